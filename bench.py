@@ -12,12 +12,38 @@ select configs[1] / configs[4].
 Timed region: ba_solve_prepared() with max_num_iterations = K and the
 convergence tolerances disabled, so exactly K LM iterations run on a window
 already resident in HBM (ba_prepare(), the host structure build + upload, is
-timed separately as setup_ms). Five timed runs after the warmup; value is the
-median (BASELINE.md's protocol). Each timed run is preceded by one untimed
-re-solve of the same prepared window (identical work from the same prepared
-start; MIBA_BENCH_WARM_EACH=0 turns it off): the host-side prepare leaves the
+timed separately as setup_ms). Should the LM loop end before K iterations (once
+the window has converged to rounding error the loop stops by itself, on C4
+after ~31 iterations, a count that varies from run to run with the rounding of
+the atomic sums), the timed region solves the same prepared window again, from
+the same prepared start, until exactly K iterations have run; its last solve is
+asked for exactly LAST_SOLVE_STEPS iterations, which every run reaches, so that
+what it returns does not depend on where the earlier solves ended. A plain run
+times the K steps once, after REHEARSALS short untimed passes of the same
+sequence (the first pass after the warmup is 2-3 % slower than the later ones);
+--full times them five times and reports the median (BASELINE.md's protocol).
+Each timed run is preceded by one untimed re-solve of the same prepared window
+(the same work from the same prepared start, at most WARM_STEPS_MAX iterations;
+MIBA_BENCH_WARM_EACH=0 turns it off): the host-side prepare leaves the
 GPU idle for ~20 ms, and without it the timed solve runs ~3.5 % slower while
 the clocks ramp back up (profiles/r02_bench_c4_warm_ab.txt).
+
+A plain run does only that: set-up, warmup, the K timed steps, the result line.
+--full adds everything else the line can carry, each in runs of its own: the
+per-kernel breakdown and the roofline of the dominant kernel and the Jacobian
+pass (HIP events), the end-to-end ba_solve legs (new window / repeated window),
+the repeat-prepare times and the CPU oracle baseline (--no-profile and
+--no-cpu-baseline drop a part of it again).
+
+--dump-outputs DIR writes what the last timed solve returned to its caller as
+DIR/<name>.npy (float64): cams, points, intr (the optimised window, updated in
+place by ba_solve_prepared) and summary (initial_cost, final_cost,
+num_iterations, num_successful_steps, num_unsuccessful_steps, termination_type
+of that solve). The inputs are seeded and the last solve runs the same number of
+iterations from the same start on every run, so two runs with the same arguments
+agree to rounding (the atomic sums) and two builds can be compared array for
+array. At most DUMP_MAX_BYTES are written: of a larger
+array a fixed, seeded sample of rows.
 
 --gpus N (one rank per GPU, RCCL over xGMI; under torchrun WORLD_SIZE must equal N, and without a launcher
 bench.py starts the N rank processes itself, after checking that N devices are visible — it refuses, exit 2, rather
@@ -33,7 +59,9 @@ N-times larger window (same cameras), value = LM iterations/s of that window.
 --config C1 / C3 (TUM-size stand-ins, ≈10 / 50 keyframes): latency of the
 reference's per-frame call instead (main.cpp:163-168 re-optimises the same
 window every frame): ms per full ba_solve (prepare + LM to convergence, default
-tolerances) and per ba_solve_prepared re-solve of the resident window.
+tolerances), a step being one such solve; with --full also per repeated ba_solve
+and per ba_solve_prepared re-solve of the resident window, with the per-kernel
+breakdown and the CPU oracle's time.
 """
 from __future__ import annotations
 
@@ -51,7 +79,11 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 F64_MFMA_PEAK_TF = 78.6  # MI355X FP64 matrix spec (tools/mfma_f64_rate.hip measures ~73 TF/s sustained)
-TIMED_RUNS = 5
+TIMED_RUNS = 5           # --full; a plain run times the steps once
+REHEARSALS = 4           # untimed passes of the timed sequence before a plain run's one timed pass
+WARM_STEPS_MAX = 256     # LM iterations of the untimed re-solve before a timed run (~60 ms of GPU work on C4)
+LAST_SOLVE_STEPS = 20    # iterations of the last solve of a timed run: the window is not converged before them
+DUMP_MAX_BYTES = 48 << 20
 
 # kernels whose bound is HBM bandwidth (per-observation passes) vs the f64 matrix cores
 HBM_KERNELS = {"cam_side", "cam_reduce", "point_colnorm", "point_prep", "backsub_eval", "lin_finalize", "scale", "assemble",
@@ -71,10 +103,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C4", choices=["C1", "C2", "C3", "C4", "C5"])
     ap.add_argument("--weak", action="store_true", help="weak scaling: a C4-size landmark block per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel breakdown, roofline, "
+                         "end-to-end and repeat-prepare legs, CPU baseline; five timed runs (median) instead of one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed solve returned as DIR/<name>.npy")
     ap.add_argument("--cpu-iters", type=int, default=4, help="LM iterations per timed run of the CPU oracle sample")
     ap.add_argument("--cpu-runs", type=int, default=3, help="timed runs of each CPU leg (median)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="disable per-kernel HIP events")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle legs")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: disable per-kernel HIP events")
     ap.add_argument("--shard", action="store_true", help="landmark-sharded path even on one GPU")
     ap.add_argument("--problem", default=None,
                     help="bench a window file instead of a synthetic config: a .miba dump (MIBA_DUMP_DIR capture, "
@@ -190,35 +227,147 @@ def cpu_baseline(prob0, args, file_opts) -> dict:
     return out
 
 
-def time_runs(solver, prob0, steps, runs):
-    """ba_prepare (setup) + ba_solve_prepared of exactly `steps` iterations, `runs` times."""
+def solve_steps(solver, bufs, steps):
+    """ba_solve_prepared of the resident window until exactly `steps` LM iterations have run: one call when
+    steps <= LAST_SOLVE_STEPS. A longer run does not fit one call (a converged window ends the LM loop by itself,
+    after a number of iterations that varies with the rounding of the atomic sums, and leaves parameters that
+    differ by more than rounding when that number differs), so it solves the same window again and again from the
+    same prepared start into bufs[1], each call asked for all that remains of steps - LAST_SOLVE_STEPS, and then,
+    as its last solve, for exactly LAST_SOLVE_STEPS iterations into bufs[0]: a count every run reaches, so that
+    what the last solve returns is the same on every run. Returns that last solve's summary and the number of
+    calls."""
+    tail = min(steps, LAST_SOLVE_STEPS)
+    done, calls = 0, 0
+
+    def call(ask, buf):
+        nonlocal done, calls
+        if solver.options.max_num_iterations != ask:
+            solver.set_options(max_num_iterations=ask)
+        summ = solver.solve_prepared(buf)
+        calls += 1
+        if summ["num_iterations"] < 1:
+            raise SystemExit(f"bench.py: the LM loop ran no iteration ({summ['message']}): nothing to time")
+        done += summ["num_iterations"]
+        return summ
+
+    while done < steps - tail:
+        call(steps - tail - done, bufs[1])
+    summ = call(tail, bufs[0])
+    while done < steps:  # the last solve ended before its count (not seen so far): make the count up
+        call(steps - done, bufs[1])
+    return summ, calls
+
+
+def time_runs(solver, prob0, steps, runs, rehearsals=0):
+    """ba_prepare (setup) + ba_solve_prepared of exactly `steps` iterations, `runs` times. Also returns the last
+    run's summary, number of ba_solve_prepared calls and problem (the arrays that run updated in place).
+    `rehearsals` untimed passes of the same sequence come first, their solves cut to WARM_STEPS_MAX iterations:
+    the first pass after the warmup runs 2-3 % slower than the later ones (the timed_runs list of a --full line
+    shows it), so a run that times the steps only once rehearses them first."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size() if dist.is_initialized() else 1
-    el, setup, summ = [], [], None
+    el, setup, summ, calls, prob = [], [], None, 0, None
     # setup_ms is the cost of a NEW window: the plan is rebuilt on every prepare (rebuild_plan = 1)
     solver.set_options(max_num_iterations=steps, profile_kernels=0, rebuild_plan=1)
-    for _ in range(runs):
+    # where the solves before a run's last one write their outputs: made once, here, and nothing large is freed
+    # between t0 and t1 (releasing the previous pass's window there cost a 20-step run ~6 ms)
+    spare = prob0.copy() if steps > LAST_SOLVE_STEPS else None
+    for i in range(rehearsals + runs):
+        n = steps if i >= rehearsals else min(steps, WARM_STEPS_MAX)
         prob = prob0.copy()
         ts = time.perf_counter()
         solver.prepare(prob)
-        setup.append((time.perf_counter() - ts) * 1e3)
+        te = time.perf_counter()
         if os.environ.get("MIBA_BENCH_WARM_EACH", "1") == "1":
-            # untimed re-solve of the same prepared window (identical work, from the same prepared start):
+            # untimed re-solve of the same prepared window (the same work, from the same prepared start):
             # the host-side prepare above leaves the GPU idle for ~20 ms, and the timed solve should not
             # pay for its clocks ramping back up
+            solver.set_options(max_num_iterations=min(n, WARM_STEPS_MAX))
             solver.solve_prepared(prob.copy())
+            solver.set_options(max_num_iterations=n)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        summ = solver.solve_prepared(prob)
+        summ, calls = solve_steps(solver, (prob, spare), n)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if world > 1:
             dist.barrier()
-        el.append(t1 - t0)
-    return el, setup, summ
+        if i >= rehearsals:
+            setup.append((te - ts) * 1e3)
+            el.append(t1 - t0)
+    return el, setup, summ, calls, prob
+
+
+def summary_array(summ):
+    import numpy as np
+    return np.array([summ["initial_cost"], summ["final_cost"], summ["num_iterations"], summ["num_successful_steps"],
+                     summ["num_unsuccessful_steps"], summ["termination_type"]], dtype=np.float64)
+
+
+def dump_outputs(out_dir, prob, summ):
+    """--dump-outputs: the window as the last timed solve left it (cams, points, intr: updated in place, what a
+    caller of ba_solve / ba_solve_prepared receives) and that solve's summary, one float64 .npy each. An array over
+    its share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of its rows (the same rows on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"cams": prob.cams, "points": prob.points, "intr": prob.intr, "summary": summary_array(summ)}
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            rows = share // max(a[0].nbytes, 1)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def full_fields(args, world, prob0, file_opts, stats, live, dom, jac, wsumm, e2e, e2e_it, e2e_rep, e2e_rep_it,
+                rep_prep, setups_rep, rep_info) -> dict:
+    """--full: what the result line carries beside the headline figure (the CPU oracle legs run here)."""
+    kern = [k for k in stats if k["launches"] > 0]
+    roofs = {k["name"]: roofline_entry(k, args.config) for k in kern}
+    jr = roofs.get(jac)
+    if jr is not None and jr.get("avg_launch_ms"):
+        # SURVEY.md 8(d): the fused pass never writes J, so achieved / frac count only the bytes it moves
+        # (bytes_per_launch, the algorithmic model; traffic = the PMC-measured HBM bytes beside it)
+        us = jr["avg_launch_ms"] * 1e3
+        jr["basis"] = "bytes the fused pass moves (J recomputed in registers, never written)"
+        if jr.get("flops_per_launch"):
+            # the pass is f64 VALU work (lin_obs + the Gram sums); same 78.6 TF/s peak as the f64 MFMA
+            jr["valu_f64"] = {"achieved_tflops": round(jr["flops_per_launch"] / (us * 1e-6) / 1e12, 3),
+                              "peak_tflops": F64_MFMA_PEAK_TF,
+                              "frac": round(jr["flops_per_launch"] / (us * 1e-6) / 1e12 / F64_MFMA_PEAK_TF, 4)}
+    cpu = None
+    if not args.no_cpu_baseline and world == 1:
+        cpu = cpu_baseline(prob0, args, file_opts)
+    wit = max(wsumm["num_iterations"], 1)
+    phases = {k["name"]: round(k["total_ms"] / wit, 4) for k in live}  # breakdown run, every kernel timed
+    return {
+        "end_to_end_ms": round(statistics.median(e2e), 3),
+        "end_to_end": {"what": "ba_solve = ba_prepare + LM to termination with the reference settings "
+                               "(tolerances 1e-6 / 1e-10 / 1e-8, max 75 iterations), warm context, median of 3; "
+                               "a new window every call (the host plan rebuilt: rebuild_plan = 1)",
+                       "lm_iterations": e2e_it, "runs_ms": [round(v, 3) for v in e2e]},
+        "setup_ms_repeat": round(statistics.median(setups_rep), 3),
+        "end_to_end_repeat_ms": round(statistics.median(e2e_rep), 3),
+        "end_to_end_repeat": {"what": "the reference's per-frame re-solve of the same window (main.cpp:163-168): "
+                                      "ba_solve of an unchanged window structure, the plan cache reuses the host "
+                                      "plan and the device structure (rebuild_plan = 0) and uploads the parameters",
+                              "lm_iterations": e2e_rep_it, "runs_ms": [round(v, 3) for v in e2e_rep],
+                              "plan_reused": [int(i["plan_reused"]) for i in rep_prep],
+                              "prepare": {k: (round(v, 4) if isinstance(v, float) else v)
+                                          for k, v in rep_info.items()}},
+        "roofline": roofs.get(dom),
+        "roofline_source": "libmiba HIP events (solver stream) around every launch of the dominant kernel and of "
+                           "the Jacobian pass, over a repeat of the timed K-step region",
+        "roofline_jacobian_pass": roofs.get(jac),
+        "cpu_baseline": cpu,
+        "kernel_ms_per_step": phases,
+        "kernel_ms_per_step_source": f"breakdown run after warmup ({wit} LM iterations, every launch timed with "
+                                     f"HIP events)",
+    }
 
 
 def latency_bench(args):
@@ -226,7 +375,6 @@ def latency_bench(args):
     import torch
     from miba import synthetic
     from miba.solver import Solver
-    from oracle import oracle
     torch.cuda.set_device(0)
     prob0 = synthetic.make_config(args.config)
     opts = dict(minimizer_progress_to_stdout=0)
@@ -234,35 +382,34 @@ def latency_bench(args):
         for _ in range(max(args.warmup, 1)):
             s.solve(prob0.copy())
         full, repeat, resolve, its = [], [], [], []
-        for rebuild, out in ((1, full), (0, repeat)):  # a new window per call / the same window again (plan cache)
+        # a new window per call; --full: also the same window again (plan cache)
+        for rebuild, out in ((1, full), (0, repeat)) if args.full else ((1, full),):
             s.set_options(rebuild_plan=rebuild)
-            for _ in range(max(args.steps, 5)):
+            for _ in range(args.steps):
                 q = prob0.copy()
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 sm = s.solve(q)
                 out.append((time.perf_counter() - t0) * 1e3)
                 its.append(sm["num_iterations"])
-        q = prob0.copy()
-        s.prepare(q)
-        for _ in range(max(args.steps, 5)):
-            t0 = time.perf_counter()
-            s.solve_prepared(q)
-            resolve.append((time.perf_counter() - t0) * 1e3)
-        # per-kernel breakdown of one profiled re-solve (HIP events around every launch; not the timed runs)
-        s.set_options(profile_kernels=1, profile_mask=0)
-        s.reset_kernel_stats()
-        sp = s.solve_prepared(prob0.copy())
-        breakdown = {k["name"]: round(k["total_ms"] * 1e3 / max(sp["num_iterations"], 1), 2)
-                     for k in s.kernel_stats() if k["launches"] > 0}
-        s.set_options(profile_kernels=0)
-    oracle.config(1, True)
-    cpu = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        so = oracle.solve(prob0.copy())
-        cpu.append((time.perf_counter() - t0) * 1e3)
-    oracle.config(1, False)
+                if out is full:
+                    last = (q, sm)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *last)
+        if args.full:
+            q = prob0.copy()
+            s.prepare(q)
+            for _ in range(args.steps):
+                t0 = time.perf_counter()
+                s.solve_prepared(q)
+                resolve.append((time.perf_counter() - t0) * 1e3)
+            # per-kernel breakdown of one profiled re-solve (HIP events around every launch; not the timed runs)
+            s.set_options(profile_kernels=1, profile_mask=0)
+            s.reset_kernel_stats()
+            sp = s.solve_prepared(prob0.copy())
+            breakdown = {k["name"]: round(k["total_ms"] * 1e3 / max(sp["num_iterations"], 1), 2)
+                         for k in s.kernel_stats() if k["launches"] > 0}
+            s.set_options(profile_kernels=0)
     med = statistics.median
     out = {"metric": "ms per windowOptimize solve (prepare + LM to convergence)", "value": round(med(full), 4),
            "unit": "ms", "n_gpus": 1, "steps": len(full), "warmup": args.warmup, "ms_per_step": round(med(full), 4),
@@ -271,16 +418,27 @@ def latency_bench(args):
                                   f"{prob0.n_obs} obs (synthetic.make_config; real TUM windows need the dataset and "
                                   f"the OpenCV/OpenGV front-end, absent offline)", "cams": prob0.n_cams,
                       "points": prob0.n_points, "obs": prob0.n_obs, "parallelism": "single"},
-           "lm_iterations": its[0], "ms_per_resolve_prepared": round(med(resolve), 4),
-           "ms_per_lm_iteration": round(med(full) / max(its[0], 1), 4),
-           "ms_per_repeat_solve": round(med(repeat), 4),
-           "kernel_us_per_lm_iteration": breakdown,
-           "what": "value: ba_solve of a new window (host plan rebuilt, rebuild_plan = 1); ms_per_repeat_solve: "
-                   "ba_solve of the same window again, the reference's per-frame call (main.cpp:163-168), plan cache "
-                   "on; ms_per_resolve_prepared: ba_solve_prepared of the resident window",
-           "cpu_baseline": {"value": round(med(cpu), 3), "unit": "ms", "cores": 1, "kind": "port",
-                            "sample": f"oracle full solve of the same window ({so['num_iterations']} LM iterations), "
-                                      f"median of 3", "host": host_info()}}
+           "lm_iterations": its[0], "ms_per_lm_iteration": round(med(full) / max(its[0], 1), 4),
+           "what": "value: ba_solve of a new window (host plan rebuilt, rebuild_plan = 1)"}
+    if args.full:
+        from oracle import oracle
+        oracle.config(1, True)
+        cpu = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            so = oracle.solve(prob0.copy())
+            cpu.append((time.perf_counter() - t0) * 1e3)
+        oracle.config(1, False)
+        out.update({
+            "ms_per_resolve_prepared": round(med(resolve), 4),
+            "ms_per_repeat_solve": round(med(repeat), 4),
+            "kernel_us_per_lm_iteration": breakdown,
+            "what": out["what"] + "; ms_per_repeat_solve: ba_solve of the same window again, the reference's "
+                    "per-frame call (main.cpp:163-168), plan cache on; ms_per_resolve_prepared: ba_solve_prepared "
+                    "of the resident window",
+            "cpu_baseline": {"value": round(med(cpu), 3), "unit": "ms", "cores": 1, "kind": "port",
+                             "sample": f"oracle full solve of the same window ({so['num_iterations']} LM "
+                                       f"iterations), median of 3", "host": host_info()}})
     print(json.dumps(out), flush=True)
 
 
@@ -441,6 +599,9 @@ def free_port() -> int:
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be at least 1 and --warmup at least 0", file=sys.stderr)
+        raise SystemExit(2)
     latency = args.config in ("C1", "C3") and not args.problem
     if os.environ.get("WORLD_SIZE") is None and (args.gpus or 1) > 1:
         # counted from sysfs: the parent never imports torch or loads the HIP runtime
@@ -485,7 +646,7 @@ def main():
         prob = shard.split_landmarks(whole, world, rank)[0] if world > 1 else whole
     prob0 = prob.copy()
 
-    prof = 0 if args.no_profile else 1
+    prof = 1 if args.full and not args.no_profile else 0
     solver = Solver(file_opts, device=local_rank, profile_kernels=prof, max_num_iterations=max(args.warmup, 1),
                     **NO_TOL)
     if sharded:
@@ -499,23 +660,27 @@ def main():
         prob = prob0.copy()
         solver.prepare(prob)
         solver.solve_prepared(prob)
-    # breakdown run: every kernel launch timed (per-iteration breakdown, dominant kernel)
-    solver.set_options(max_num_iterations=5, profile_kernels=prof, profile_mask=0)
-    prob = prob0.copy()
-    solver.prepare(prob)
-    solver.reset_kernel_stats()
-    wsumm = solver.solve_prepared(prob)
-    wstats = solver.kernel_stats()
-    names = [k["name"] for k in wstats]
-    live = [k for k in wstats if k["launches"] > 0]
-    dom = max(live, key=lambda k: k["total_ms"])["name"] if live else None
-    jac = next((nm for nm in JACOBIAN_PASSES if any(k["name"] == nm for k in live)), JACOBIAN_PASSES[-1])
+    if args.full:
+        # breakdown run: every kernel launch timed (per-iteration breakdown, dominant kernel)
+        solver.set_options(max_num_iterations=5, profile_kernels=prof, profile_mask=0)
+        prob = prob0.copy()
+        solver.prepare(prob)
+        solver.reset_kernel_stats()
+        wsumm = solver.solve_prepared(prob)
+        wstats = solver.kernel_stats()
+        names = [k["name"] for k in wstats]
+        live = [k for k in wstats if k["launches"] > 0]
+        dom = max(live, key=lambda k: k["total_ms"])["name"] if live else None
+        jac = next((nm for nm in JACOBIAN_PASSES if any(k["name"] == nm for k in live)), JACOBIAN_PASSES[-1])
     # timed runs (no HIP events: event records between dependent launches cost ~5-10 us each)
-    els, setups, summ = time_runs(solver, prob0, args.steps, TIMED_RUNS)
+    runs, rehearsals = (TIMED_RUNS, 0) if args.full else (1, REHEARSALS)
+    els, setups, summ, calls, solved = time_runs(solver, prob0, args.steps, runs, rehearsals)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solved, summ)
     # the same K-step region again with HIP events around the dominant kernel and the
     # Jacobian pass only: their average launch durations for the roofline
     stats = []
-    if prof:
+    if args.full and prof:
         mask = 0
         for nm in (dom, jac):
             if nm in names:
@@ -544,50 +709,33 @@ def main():
             its = se["num_iterations"]
             prep.append(solver.last_prepare())
         return out[1:], its, prep[1:]  # the first call may grow buffers / build the plan
-    e2e, e2e_it, _ = e2e_leg(1)
-    e2e_rep, e2e_rep_it, rep_prep = e2e_leg(0)
-    setups_rep = []
-    solver.set_options(max_num_iterations=args.steps, rebuild_plan=0, **NO_TOL)
-    for _ in range(TIMED_RUNS):
-        q = prob0.copy()  # the caller's arrays exist before the call (as in time_runs)
-        ts = time.perf_counter()
-        solver.prepare(q)
-        setups_rep.append((time.perf_counter() - ts) * 1e3)
-    rep_info = solver.last_prepare()
-    iters = summ["num_iterations"]
+    if args.full:
+        e2e, e2e_it, _ = e2e_leg(1)
+        e2e_rep, e2e_rep_it, rep_prep = e2e_leg(0)
+        setups_rep = []
+        solver.set_options(max_num_iterations=args.steps, rebuild_plan=0, **NO_TOL)
+        for _ in range(TIMED_RUNS):
+            q = prob0.copy()  # the caller's arrays exist before the call (as in time_runs)
+            ts = time.perf_counter()
+            solver.prepare(q)
+            setups_rep.append((time.perf_counter() - ts) * 1e3)
+        rep_info = solver.last_prepare()
+    iters = args.steps  # solve_steps ran exactly that many, in `calls` ba_solve_prepared calls
     elapsed = statistics.median(els)
-    t = torch.tensor([elapsed, float(iters)], dtype=torch.float64, device="cuda")
+    t = torch.tensor([elapsed, float(calls)], dtype=torch.float64, device="cuda")
     if world > 1:
         tmax = t.clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         tmin = t.clone()
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         elapsed_max = float(tmax[0])
-        assert float(tmin[1]) == float(tmax[1]) == float(iters), "ranks ran different iteration counts"
+        assert float(tmin[1]) == float(tmax[1]) == float(calls), "ranks ran different iteration counts"
     else:
         elapsed_max = elapsed
 
     if rank == 0:
         value = iters / elapsed_max
         ms_per_step = elapsed_max * 1e3 / max(iters, 1)
-        kern = [k for k in stats if k["launches"] > 0]
-        roofs = {k["name"]: roofline_entry(k, args.config) for k in kern}
-        jr = roofs.get(jac)
-        if jr is not None and jr.get("avg_launch_ms"):
-            # the fused pass never writes J, so achieved / frac count only the bytes it moves
-            # (bytes_per_launch, the algorithmic model; traffic = the PMC-measured HBM bytes beside it)
-            us = jr["avg_launch_ms"] * 1e3
-            jr["basis"] = "bytes the fused pass moves (J recomputed in registers, never written)"
-            if jr.get("flops_per_launch"):
-                # the pass is f64 VALU work (lin_obs + the Gram sums); same 78.6 TF/s peak as the f64 MFMA
-                jr["valu_f64"] = {"achieved_tflops": round(jr["flops_per_launch"] / (us * 1e-6) / 1e12, 3),
-                                  "peak_tflops": F64_MFMA_PEAK_TF,
-                                  "frac": round(jr["flops_per_launch"] / (us * 1e-6) / 1e12 / F64_MFMA_PEAK_TF, 4)}
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            cpu = cpu_baseline(prob0, args, file_opts)
-        wit = max(wsumm["num_iterations"], 1)
-        phases = {k["name"]: round(k["total_ms"] / wit, 4) for k in live}  # breakdown run, every kernel timed
         n_cams = prob0.n_cams
         n_pts = whole.n_points if whole is not None else world * prob0.n_points
         n_obs = whole.n_obs if whole is not None else world * prob0.n_obs
@@ -620,36 +768,20 @@ def main():
                        "parallelism": f"landmark-shard{world}" if sharded else "single",
                        "obs_record": obs_record(prob0)},
             "setup_ms": round(statistics.median(setups), 3),
-            "end_to_end_ms": round(statistics.median(e2e), 3),
-            "end_to_end": {"what": "ba_solve = ba_prepare + LM to termination with the reference settings "
-                                   "(tolerances 1e-6 / 1e-10 / 1e-8, max 75 iterations), warm context, median of 3; "
-                                   "a new window every call (the host plan rebuilt: rebuild_plan = 1)",
-                           "lm_iterations": e2e_it, "runs_ms": [round(v, 3) for v in e2e]},
-            "setup_ms_repeat": round(statistics.median(setups_rep), 3),
-            "end_to_end_repeat_ms": round(statistics.median(e2e_rep), 3),
-            "end_to_end_repeat": {"what": "the reference's per-frame re-solve of the same window (main.cpp:163-168): "
-                                          "ba_solve of an unchanged window structure, the plan cache reuses the host "
-                                          "plan and the device structure (rebuild_plan = 0) and uploads the parameters",
-                                  "lm_iterations": e2e_rep_it, "runs_ms": [round(v, 3) for v in e2e_rep],
-                                  "plan_reused": [int(i["plan_reused"]) for i in rep_prep],
-                                  "prepare": {k: (round(v, 4) if isinstance(v, float) else v)
-                                              for k, v in rep_info.items()}},
             "timed_runs": {"n": len(els), "ms_per_step": [round(e * 1e3 / max(iters, 1), 4) for e in els],
                            "statistic": "median"},
-            "roofline": roofs.get(dom),
-            "roofline_source": "libmiba HIP events (solver stream) around every launch of the dominant kernel and of "
-                               "the Jacobian pass, over a repeat of the timed K-step region",
-            "roofline_jacobian_pass": roofs.get(jac),
-            "cpu_baseline": cpu,
-            "lm": {"iterations": iters, "successful": summ["num_successful_steps"],
-                   "note": "iterations = LM steps after iteration 0; successful counts iteration 0 (Ceres convention)",
+            "lm": {"iterations": iters, "solves": calls, "last_solve_iterations": summ["num_iterations"],
+                   "successful": summ["num_successful_steps"],
+                   "note": "iterations = LM steps after iteration 0 over the `solves` ba_solve_prepared calls of a "
+                           "timed run; the other fields are the last call's; successful counts iteration 0 (Ceres "
+                           "convention)",
                    "unsuccessful": summ["num_unsuccessful_steps"], "initial_cost": summ["initial_cost"],
                    "final_cost": summ["final_cost"], "termination": summ["termination"],
                    "linear_solver": summ["linear_solver"]},
-            "kernel_ms_per_step": phases,
-            "kernel_ms_per_step_source": f"breakdown run after warmup ({wit} LM iterations, every launch timed with "
-                                         f"HIP events)",
         }
+        if args.full:
+            out.update(full_fields(args, world, prob0, file_opts, stats, live, dom, jac, wsumm, e2e, e2e_it,
+                                   e2e_rep, e2e_rep_it, rep_prep, setups_rep, rep_info))
         print(json.dumps(out), flush=True)
     solver.close()
     if world > 1:

@@ -9,7 +9,7 @@ timeout -s KILL 60 rocprofv3 -L > $O/avail.txt 2>&1 || { echo LIST_FAIL; exit 1;
 has() { grep -q -w "$1" $O/avail.txt; }
 run() {  # name counters...
     local n=$1; shift
-    timeout -s KILL 120 rocprofv3 --pmc "$@" --output-format csv -d $O/$n -o $n -- python3 bench.py --steps 10 --warmup 1 --no-profile --no-cpu-baseline > $O/$n.log 2>&1 || { echo PMC_${n}_FAIL; exit 1; }
+    timeout -s KILL 120 rocprofv3 --pmc "$@" --output-format csv -d $O/$n -o $n -- python3 bench.py --full --steps 10 --warmup 1 --no-profile --no-cpu-baseline > $O/$n.log 2>&1 || { echo PMC_${n}_FAIL; exit 1; }
     echo "pass $n: $*"
 }
 G1=(); for c in TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum; do has ${c%_sum} && G1+=($c); done
