@@ -1621,6 +1621,68 @@ extern "C" int32_t ba_last_prepare(const ba_context* ctx, ba_prepare_info* info)
     return BA_OK;
 }
 
+// ---- the enqueue code of an LM solve on the prepared window, shared by ba_solve_prepared and ba_debug_step
+static LmParams lm_params(const ba_context* ctx) {
+    const ba_options& o = ctx->opts;
+    LmParams prm{};
+    prm.min_relative_decrease = o.min_relative_decrease;
+    prm.max_radius = o.max_trust_region_radius;
+    prm.min_radius = o.min_trust_region_radius;
+    prm.function_tolerance = o.function_tolerance;
+    prm.gradient_tolerance = o.gradient_tolerance;
+    prm.parameter_tolerance = o.parameter_tolerance;
+    prm.max_iter = std::max(o.max_num_iterations, 0);
+    prm.max_invalid = o.max_num_consecutive_invalid_steps;
+    prm.progress = ctx->dprog;
+    return prm;
+}
+
+// The solve's start: the iteration log, then x and the candidate slots from the parameters of the last
+// ba_prepare() (device-to-device) and the fresh state st0.
+static int enqueue_reset(ba_context* ctx, const LmState& st0, int n_cams) {
+    DevProblem& P = ctx->P;
+    DevWork& W = ctx->W;
+    const int max_iter = std::max(ctx->opts.max_num_iterations, 0);
+    HIPCHECK(ctx, ctx->buf[B_LOG].ensure(sizeof(double) * LOG_W * (max_iter + 2)));
+    W.log = ctx->buf[B_LOG].as<double>();
+    // the split BCR kernel's flags hold 4 * epoch + panel (one epoch per launch): re-initialise the hand-off
+    // state long before 4 * epoch wraps (2^30 launches) on a context that re-solves one prepared window forever
+    if (P.solver == 2 && ctx->bcr_launches > (1ull << 28))
+        if (int rc = bcr_init_handoffs(ctx)) return rc;
+    HIPCHECK(ctx, launch_reset(P, W, st0, ctx->buf[B_CAMS_INIT].as<double>(), ctx->buf[B_PTS_INIT].as<double>(),
+                               ctx->buf[B_K_INIT].as<double>(), n_cams, ctx->dev_np, ctx->stream));
+    return BA_OK;
+}
+
+// IterationZero: cost, gradient, column norms -> Jacobi scale, |x|.
+// (fused path: S and rhs, the atomic targets of the first assembly (later ones are zeroed in-loop), were
+// zeroed by k_reset)
+static int enqueue_iteration_zero(ba_context* ctx) {
+    DevProblem& P = ctx->P;
+    DevWork& W = ctx->W;
+    hipStream_t s = ctx->stream;
+    Prof* pf = ctx->pf();
+    if (ctx->hprog) __atomic_store_n(ctx->hprog, 0u, __ATOMIC_RELEASE);
+    HIPCHECK(ctx, launch_linearize(P, ctx->C, 0, W, s, pf));
+    HIPCHECK(ctx, launch_scale(P, ctx->C, ctx->opts.jacobi_scaling, W, s, pf));
+    HIPCHECK(ctx, launch_init_state(P, W, ctx->hprog ? ctx->dprog : nullptr, s, pf));
+    return BA_OK;
+}
+
+// One LM iteration: a fixed launch sequence with device-side decisions.
+static int enqueue_iteration(ba_context* ctx, const LmParams& prm) {
+    DevProblem& P = ctx->P;
+    DevWork& W = ctx->W;
+    hipStream_t s = ctx->stream;
+    Prof* pf = ctx->pf();
+    HIPCHECK(ctx, launch_linearize(P, ctx->C, 1, W, s, pf));
+    HIPCHECK(ctx, launch_build(P, ctx->C, W, s, pf));
+    HIPCHECK(ctx, launch_factor(P, ctx->C, W, s, pf));
+    HIPCHECK(ctx, launch_update(P, ctx->C, prm, W, s, pf));
+    if (P.solver == 2 && W.bcr.persist >= 2) ++ctx->bcr_launches;
+    return BA_OK;
+}
+
 static int32_t solve_prepared(ba_context* ctx, ba_problem* p, ba_summary* sum, double t0);
 
 // the LM loop into a full-size summary, copied out at the caller's size
@@ -1667,20 +1729,11 @@ static int32_t solve_prepared(ba_context* ctx, ba_problem* p, ba_summary* sum, d
     Prof* pf = ctx->pf();
     DevProblem& P = ctx->P;
     DevWork& W = ctx->W;
-    const BaConsts& C = ctx->C;
     hipStream_t s = ctx->stream;
     const int max_iter = std::max(o.max_num_iterations, 0);
-    HIPCHECK(ctx, ctx->buf[B_LOG].ensure(sizeof(double) * LOG_W * (max_iter + 2)));
-    W.log = ctx->buf[B_LOG].as<double>();
     static thread_local LmState h_state;  // host staging (outlives the async copies)
     h_state = fresh_state(o, o.initial_trust_region_radius);
-    // the split BCR kernel's flags hold 4 * epoch + panel (one epoch per launch): re-initialise the hand-off
-    // state long before 4 * epoch wraps (2^30 launches) on a context that re-solves one prepared window forever
-    if (P.solver == 2 && ctx->bcr_launches > (1ull << 28))
-        if (int rc = bcr_init_handoffs(ctx)) return rc;
-    // start from the parameters of the last ba_prepare() (device-to-device) and a fresh state
-    HIPCHECK(ctx, launch_reset(P, W, h_state, ctx->buf[B_CAMS_INIT].as<double>(), ctx->buf[B_PTS_INIT].as<double>(),
-                               ctx->buf[B_K_INIT].as<double>(), p->n_cams, ctx->dev_np, s));
+    if (int rc = enqueue_reset(ctx, h_state, p->n_cams)) return rc;
     sum->num_obs_admissible = ctx->n_adm_all;
     sum->num_active_cams = P.nac;
     sum->num_active_points = P.n_ap;
@@ -1692,24 +1745,8 @@ static int32_t solve_prepared(ba_context* ctx, ba_problem* p, ba_summary* sum, d
     double kms0[K_COUNT];
     std::memcpy(kms0, ctx->k_ms, sizeof(kms0));
 
-    LmParams prm{};
-    prm.min_relative_decrease = o.min_relative_decrease;
-    prm.max_radius = o.max_trust_region_radius;
-    prm.min_radius = o.min_trust_region_radius;
-    prm.function_tolerance = o.function_tolerance;
-    prm.gradient_tolerance = o.gradient_tolerance;
-    prm.parameter_tolerance = o.parameter_tolerance;
-    prm.max_iter = max_iter;
-    prm.max_invalid = o.max_num_consecutive_invalid_steps;
-    prm.progress = ctx->dprog;
-    if (ctx->hprog) __atomic_store_n(ctx->hprog, 0u, __ATOMIC_RELEASE);
-
-    // fused path: S and rhs, the atomic targets of the first assembly (later ones are zeroed in-loop), were
-    // zeroed by k_reset
-    // IterationZero: cost, gradient, column norms -> Jacobi scale, |x|
-    HIPCHECK(ctx, launch_linearize(P, C, 0, W, s, pf));
-    HIPCHECK(ctx, launch_scale(P, C, o.jacobi_scaling, W, s, pf));
-    HIPCHECK(ctx, launch_init_state(P, W, ctx->hprog ? ctx->dprog : nullptr, s, pf));
+    const LmParams prm = lm_params(ctx);
+    if (int rc = enqueue_iteration_zero(ctx)) return rc;
     // LM iterations: fixed launch sequence, device-side decisions; the host follows the device.
     // Iterations enqueued after the termination are no-ops (their kernels exit at once).
     int launched = 0;
@@ -1718,11 +1755,7 @@ static int32_t solve_prepared(ba_context* ctx, ba_problem* p, ba_summary* sum, d
     LmState& S = h_state;
     const bool shard = W.comm.on();
     auto launch_iter = [&]() -> int {
-        HIPCHECK(ctx, launch_linearize(P, C, 1, W, s, pf));
-        HIPCHECK(ctx, launch_build(P, C, W, s, pf));
-        HIPCHECK(ctx, launch_factor(P, C, W, s, pf));
-        HIPCHECK(ctx, launch_update(P, C, prm, W, s, pf));
-        if (P.solver == 2 && W.bcr.persist >= 2) ++ctx->bcr_launches;
+        if (int rc = enqueue_iteration(ctx, prm)) return rc;
         ++launched;
         return BA_OK;
     };
@@ -1953,6 +1986,69 @@ extern "C" int32_t ba_debug_camera_sums(ba_context* ctx, const ba_problem* p, in
     HIPCHECK(ctx, hipMemcpyAsync(lin, ctx->W.lin, sizeof(double) * LIN_N, hipMemcpyDeviceToHost, s));
     HIPCHECK(ctx, hipStreamSynchronize(s));
     if (ac_cam) std::copy(ctx->ac_cam.begin(), ctx->ac_cam.end(), ac_cam);
+    return BA_OK;
+}
+
+extern "C" int32_t ba_debug_step(ba_context* ctx, const ba_problem* p, double radius, int32_t* nac, int32_t* ac_cam,
+                                 double* delta_cam, double* delta_intr, double* delta_pts, double* log_row,
+                                 int32_t* info) {
+    if (!ctx) return BA_E_INVALID;
+    if (!p || !nac || !ac_cam || !delta_cam || !delta_intr || !delta_pts || !log_row || !info) {
+        ctx->err = "ba_debug_step: null argument";
+        return BA_E_INVALID;
+    }
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = apply_spin_limit(ctx)) return rc;
+    if (int rc = prepare(ctx, p)) return rc;
+    ctx->err.clear();
+    DevProblem& P = ctx->P;
+    DevWork& W = ctx->W;
+    hipStream_t s = ctx->stream;
+    static thread_local LmState h_st;
+    h_st = fresh_state(ctx->opts, radius > 0 ? radius : ctx->opts.initial_trust_region_radius);
+    const int base = h_st.cur;  // the slot of x; the step's candidate goes to the other one, whatever the decision
+    const LmParams prm = lm_params(ctx);
+    // iteration zero and the first LM iteration, as ba_solve_prepared enqueues them
+    if (int rc = enqueue_reset(ctx, h_st, p->n_cams)) return rc;
+    if (int rc = enqueue_iteration_zero(ctx)) return rc;
+    int retried = 0;
+    for (;;) {
+        if (int rc = enqueue_iteration(ctx, prm)) return rc;
+        HIPCHECK(ctx, hipMemcpyAsync(&h_st, W.st, sizeof(LmState), hipMemcpyDeviceToHost, s));
+        HIPCHECK(ctx, hipStreamSynchronize(s));
+        flush_prof(ctx);
+        // a resident-kernel hand-off timed out: the iteration again with the per-level launches (once: they
+        // have no inter-workgroup waits)
+        if (!(h_st.done && h_st.msg == MSG_TIMEOUT && h_st.termination < 0) || retried) break;
+        if (int rc = bcr_timeout_retry(ctx, h_st)) return rc;
+        retried = 1;
+    }
+    if (h_st.msg == MSG_TIMEOUT) {
+        ctx->err = "ba_debug_step: the re-run iteration timed out again";
+        return BA_E_INTERNAL;
+    }
+    const size_t np3 = 3 * (size_t)p->n_points;
+    std::vector<double> dl((size_t)P.n), x0(np3), x1(np3);
+    double lg[LOG_W] = {};
+    int cf = 0;
+    if (P.n) HIPCHECK(ctx, hipMemcpyAsync(dl.data(), W.delta, sizeof(double) * P.n, hipMemcpyDeviceToHost, s));
+    if (np3) {
+        const size_t off = 3 * (size_t)ctx->gather_off;
+        HIPCHECK(ctx, hipMemcpyAsync(x0.data(), P.pts[base] + off, sizeof(double) * np3, hipMemcpyDeviceToHost, s));
+        HIPCHECK(ctx, hipMemcpyAsync(x1.data(), P.pts[base ^ 1] + off, sizeof(double) * np3, hipMemcpyDeviceToHost, s));
+    }
+    if (h_st.iter >= 1) HIPCHECK(ctx, hipMemcpyAsync(lg, W.log + LOG_W, sizeof(lg), hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, hipMemcpyAsync(&cf, W.chol_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, hipStreamSynchronize(s));
+    *nac = P.nac;
+    std::copy(ctx->ac_cam.begin(), ctx->ac_cam.begin() + P.nac, ac_cam);
+    std::copy(dl.begin(), dl.begin() + 6 * (size_t)P.nac, delta_cam);
+    std::copy(dl.begin() + P.kb, dl.begin() + P.kb + 4, delta_intr);
+    // (points without an admissible observation are never written: both slots hold the prepared value)
+    for (size_t i = 0; i < np3; ++i) delta_pts[i] = x1[i] - x0[i];
+    std::copy(lg, lg + LOG_W, log_row);
+    const int32_t inf[BA_STEP_INFO_N] = {cf, retried, P.solver, P.cam_band, P.solver == 1 ? P.band_w : 0, h_st.iter, 0, 0};
+    std::copy(inf, inf + BA_STEP_INFO_N, info);
     return BA_OK;
 }
 

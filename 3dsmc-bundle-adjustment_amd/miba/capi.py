@@ -24,6 +24,9 @@ BA_FAILURE = 2
 
 TERMINATION_NAMES = {0: "CONVERGENCE", 1: "NO_CONVERGENCE", 2: "FAILURE"}
 
+# columns of an iteration-log row (ba_iteration_log, ba_debug_step), BA_LOG_WIDTH = 8 with the last one unused
+LOG_FIELDS = ("cost", "cost_change", "gradient_max_norm", "step_norm", "tr_ratio", "tr_radius", "accepted")
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .capi import BaKernelStat, BaOptions, BaPrepareInfo, BaSummary, ProblemArrays
+from .capi import LOG_FIELDS, BaKernelStat, BaOptions, BaPrepareInfo, BaSummary, ProblemArrays
 
 
 def default_options(**overrides) -> BaOptions:
@@ -173,6 +173,28 @@ class Solver:
         self._check(self._L.ba_debug_linearize(self._h, C.byref(ps), _dptr(cost), _dptr(res), _dptr(jc), _dptr(jp),
                                                _dptr(jk)), "ba_debug_linearize")
         return dict(cost=float(cost[0]), res=res, jcam=jc, jpt=jp, jint=jk)
+
+    def lm_step(self, prob: ProblemArrays, radius: float = 0.0) -> dict:
+        """The production LM step of the window's first iteration (ba_debug_step), on the paths the prepare
+        chose: ac_cam (nac,), delta_cam (nac, 6), delta_intr (4,), delta_pts (n_points, 3) in parameter space,
+        row 1 of the iteration log by name (LOG_FIELDS, ``accepted`` as int), the factorisation ``flag``,
+        ``retried``, and the window's ``linear_solver``, ``camera_band``, ``band_tiles`` (banded Cholesky only) and
+        ``num_iterations``. ``prob`` is not modified."""
+        ps = prob.struct()
+        nc = max(prob.n_cams, 1)
+        ac = np.zeros(nc, dtype=np.int32); dc = np.zeros((nc, 6)); dk = np.zeros(4)
+        dpt = np.zeros((prob.n_points, 3)); row = np.zeros(_lib.LOG_WIDTH)
+        n = C.c_int32(0)
+        info = np.zeros(8, dtype=np.int32)  # BA_STEP_INFO_N
+        self._check(self._L.ba_debug_step(self._h, C.byref(ps), radius, C.byref(n),
+                                          ac.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(dc), _dptr(dk), _dptr(dpt),
+                                          _dptr(row), info.ctypes.data_as(C.POINTER(C.c_int32))), "ba_debug_step")
+        out = dict(ac_cam=ac[: n.value].copy(), delta_cam=dc[: n.value].copy(), delta_intr=dk, delta_pts=dpt,
+                   flag=int(info[0]), retried=int(info[1]), linear_solver=int(info[2]), camera_band=int(info[3]),
+                   band_tiles=int(info[4]), num_iterations=int(info[5]))
+        out.update({k: float(v) for k, v in zip(LOG_FIELDS, row)})
+        out["accepted"] = int(row[6])
+        return out
 
     def camera_sums(self, prob: ProblemArrays):
         """The production camera-side pass (ba_debug_camera_sums): per active camera U (6x6), C (6x4), g (6),

@@ -302,6 +302,28 @@ int32_t ba_debug_reduced_system(ba_context* ctx, const ba_problem* prob, double 
 int32_t ba_debug_camera_sums(ba_context* ctx, const ba_problem* prob, int32_t* nac, double* camdata,
                              double* lin, int32_t* ac_cam);
 
+/* Test hook: the production LM step. Prepares the window and enqueues what ba_solve_prepared enqueues for
+ * iteration zero and the first LM iteration (the same code), on the paths the prepare chose for the window
+ * (reduced solve, band tail, fused / small-window linearisation, deterministic slabs, landmark shards);
+ * radius replaces initial_trust_region_radius when > 0. prob is not modified. Outputs (all required):
+ *   nac, ac_cam[n_cams]      active cameras, in increasing order (the first *nac entries are written)
+ *   delta_cam[n_cams*6]      the parameter-space step -scale*y of active camera t at 6*t
+ *   delta_intr[4]            the same for fx, fy, cx, cy
+ *   delta_pts[n_points*3]    candidate point minus the point the step was computed from, in the caller's point
+ *                            order; zero for points without an admissible observation; the same whether the
+ *                            decision accepted or rejected the step
+ *   log_row[BA_LOG_WIDTH]    row 1 of the iteration log (zeros if the solve ended before a step was taken)
+ *   info[BA_STEP_INFO_N]     [0] the reduced-system factorisation flag of that iteration: bit 0 = not positive
+ *                            definite, bit 1 = an inter-workgroup hand-off timed out; [1] retried: 1 = a
+ *                            resident-kernel hand-off timed out and the iteration was re-run with the separate
+ *                            launches, as ba_solve_prepared does (the context keeps them); [2] the window's
+ *                            ba_summary.linear_solver and [3] camera_band; [4] with BA_LS_BAND the band width in
+ *                            16x16 tiles (the banded Cholesky's instantiation), else 0; [5] LM iterations
+ *                            counted (1 unless the solve ended before a step was taken); the rest 0 */
+#define BA_STEP_INFO_N 8
+int32_t ba_debug_step(ba_context* ctx, const ba_problem* prob, double radius, int32_t* nac, int32_t* ac_cam,
+                      double* delta_cam, double* delta_intr, double* delta_pts, double* log_row, int32_t* info);
+
 /* Test hook: FNV-1a digests of the last prepared window's plan arrays as the kernels read them from HBM (the
  * observation orderings, point order, tiles, chunks, segments, envelope), one per array, into out[max_n].
  * Returns the number of arrays. The host plan and the device plan (MIBA_DEVICE_PLAN) give the same digests. */

@@ -1137,5 +1137,53 @@ EXPORT int oracle_reduced_system(const ba_problem* p, const ba_options* opt, dou
     return st ? BA_E_INVALID : 0;
 }
 
+/* The first LM step in parameter space, delta = step * scale of compute_step at the problem's parameters
+ * (radius = initial_trust_region_radius unless radius > 0), in the layout of ba_debug_step:
+ * ac_cam[nac] the active cameras in increasing order, delta_cam[nac*6], delta_intr[4], delta_pts[n_points*3]
+ * (zero for points without an admissible observation), *mcc the model cost change of that step.
+ * With NULL outputs only *nac_out is set. Returns 0, or BA_E_INVALID on a failed evaluation / linear solve. */
+EXPORT int oracle_lm_step(const ba_problem* p, const ba_options* opt, double radius, int32_t* nac_out,
+                          int32_t* ac_cam, double* delta_cam, double* delta_intr, double* delta_pts, double* mcc) {
+    orc_t c;
+    if (orc_init(&c, p, opt)) { orc_free(&c); return BA_E_INVALID; }
+    if (nac_out) *nac_out = c.nac;
+    if (!delta_cam || !delta_intr || !delta_pts) { orc_free(&c); return 0; }
+    lin_t L;
+    if (lin_alloc(&L, c.n_adm)) { orc_free(&c); return BA_E_NOMEM; }
+    double cst;
+    int st = evaluate(&c, p->cams, p->points, p->intr, &L, &cst);
+    const int nl = nloc(&c);
+    double* cn = (double*)malloc(sizeof(double) * nl);
+    double* scale = (double*)malloc(sizeof(double) * nl);
+    double* diag = (double*)calloc(nl, sizeof(double));
+    double* step = (double*)malloc(sizeof(double) * nl);
+    if (radius <= 0) radius = opt->initial_trust_region_radius;
+    if (!st) {
+        colnorm_grad(&c, &L, cn, NULL);
+        for (int i = 0; i < nl; ++i) {
+            scale[i] = opt->jacobi_scaling ? 1.0 / (1.0 + sqrt(cn[i])) : 1.0;
+            const double v = cn[i] * scale[i] * scale[i];
+            diag[i] = fmin(fmax(v, opt->min_lm_diagonal), opt->max_lm_diagonal);
+        }
+        st = compute_step(&c, &L, scale, diag, radius, step);
+    }
+    if (!st) {
+        for (int i = 0; i < nl; ++i) step[i] *= scale[i];
+        if (mcc) *mcc = model_cost_change(&c, &L, step);
+        memcpy(delta_cam, step, sizeof(double) * 6 * c.nac);
+        memcpy(delta_intr, step + off_k(&c), sizeof(double) * 4);
+        memset(delta_pts, 0, sizeof(double) * 3 * p->n_points);
+        for (int i = 0; i < p->n_points; ++i)
+            if (c.pt_active[i]) memcpy(delta_pts + 3 * i, step + off_pt(&c, i), sizeof(double) * 3);
+        if (ac_cam)
+            for (int i = 0; i < p->n_cams; ++i)
+                if (c.cam_ac[i] >= 0) ac_cam[c.cam_ac[i]] = i;
+    }
+    free(cn); free(scale); free(diag); free(step);
+    lin_free(&L);
+    orc_free(&c);
+    return st ? BA_E_INVALID : 0;
+}
+
 /* exposed for unit tests of the manifold restatement */
 EXPORT void oracle_se3_plus(const double* T, const double* delta, double* out) { se3_plus(T, delta, out); }

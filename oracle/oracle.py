@@ -48,6 +48,9 @@ def lib():
         L.oracle_reduced_system.argtypes = [C.POINTER(BaProblem), C.POINTER(BaOptions), C.c_double, C.c_int32,
                                             C.c_int32, C.c_int32, C.POINTER(C.c_int32), dp, dp]
         L.oracle_reduced_system.restype = C.c_int
+        L.oracle_lm_step.argtypes = [C.POINTER(BaProblem), C.POINTER(BaOptions), C.c_double, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), dp, dp, dp, dp]
+        L.oracle_lm_step.restype = C.c_int
         L.oracle_se3_plus.argtypes = [dp, dp, dp]
         L.oracle_solve_trace.argtypes = [C.POINTER(BaProblem), C.POINTER(BaOptions), C.POINTER(BaSummary), dp,
                                          C.c_int32]
@@ -134,6 +137,24 @@ def reduced_system(prob: ProblemArrays, opts: BaOptions | None = None, radius: f
     if rc != 0:
         raise RuntimeError(f"oracle_reduced_system failed: {rc}")
     return S, rhs
+
+
+def lm_step(prob: ProblemArrays, opts: BaOptions | None = None, radius: float = 0.0) -> dict:
+    """The first LM step in parameter space (step * scale of compute_step), in the layout of
+    ``Solver.lm_step``: ac_cam, delta_cam (nac, 6), delta_intr (4), delta_pts (n_points, 3), and
+    the model cost change of that step."""
+    opts = opts or default_options()
+    ps = prob.struct()
+    n = C.c_int32(0)
+    lib().oracle_lm_step(C.byref(ps), C.byref(opts), radius, C.byref(n), None, None, None, None, None)
+    ac = np.zeros(max(n.value, 1), dtype=np.int32)
+    dc = np.zeros((max(n.value, 1), 6)); dk = np.zeros(4); dpt = np.zeros((prob.n_points, 3)); mcc = np.zeros(1)
+    rc = lib().oracle_lm_step(C.byref(ps), C.byref(opts), radius, C.byref(n), ac.ctypes.data_as(C.POINTER(C.c_int32)),
+                              _dptr(dc), _dptr(dk), _dptr(dpt), _dptr(mcc))
+    if rc != 0:
+        raise RuntimeError(f"oracle_lm_step failed: {rc}")
+    return dict(ac_cam=ac[: n.value], delta_cam=dc[: n.value], delta_intr=dk, delta_pts=dpt,
+                model_cost_change=float(mcc[0]))
 
 
 def se3_plus(T, delta):

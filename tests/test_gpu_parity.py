@@ -98,6 +98,8 @@ def test_solve_parity(solver, case):
     # converged parameters agree to the same order
     assert np.max(np.abs(p.points - q.points)) < 1e-3
     assert np.max(np.abs(p.intr - q.intr)) < 1e-2
+    # the reported cost belongs to the returned parameters
+    assert abs(solver.linearize(p)["cost"] - sg["final_cost"]) <= 1e-13 * sg["final_cost"]
 
 
 def test_repeated_same_window(solver):
