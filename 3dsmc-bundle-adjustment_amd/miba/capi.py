@@ -167,6 +167,59 @@ class BaPrepareInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+class BaCovRequest(C.Structure):
+    """Mirror of ``ba_cov_request`` (ba_covariance). ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_pairs", C.c_int32),
+        ("pair_a", _ip),
+        ("pair_b", _ip),
+        ("pair_cov", _dp),
+        ("n_points", C.c_int32),
+        ("point_idx", _ip),
+        ("point_cov", _dp),
+        ("full", _dp),
+        ("min_reciprocal_condition_number", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaCovInfo(C.Structure):
+    """Mirror of ``ba_cov_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("status", C.c_int32),
+        ("n", C.c_int32),
+        ("nac", C.c_int32),
+        ("pivot_min", C.c_double),
+        ("pivot_max", C.c_double),
+        ("cost", C.c_double),
+        ("variance_factor", C.c_double),
+        ("time_build_ms", C.c_double),
+        ("time_invert_ms", C.c_double),
+        ("time_points_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
+COV_INTR = -1  # BA_COV_INTR
+COV_OK, COV_RANK_DEFICIENT = 0, 1
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .capi import LOG_FIELDS, BaKernelStat, BaOptions, BaPrepareInfo, BaSummary, ProblemArrays
+from .capi import COV_INTR, LOG_FIELDS, BaCovInfo, BaCovRequest, BaKernelStat, BaOptions, BaPrepareInfo, BaSummary, ProblemArrays
 
 
 def default_options(**overrides) -> BaOptions:
@@ -222,3 +222,57 @@ class Solver:
         self._check(self._L.ba_debug_reduced_system(self._h, C.byref(ps), radius, C.byref(n), _dptr(S), _dptr(rhs)),
                     "ba_debug_reduced_system")
         return S, rhs
+
+    def covariance(self, prob: ProblemArrays, pairs=None, points=None, full: bool = False,
+                   min_rcond: float = 0.0) -> dict:
+        """Covariance of the estimate at ``prob``'s parameters (ba_covariance; ``prob`` is not modified).
+
+        ``pairs``: (a, b) camera indices of the window, ``COV_INTR`` (-1) for the intrinsics; default every active
+        camera's diagonal block plus the intrinsics block. ``points``: point indices, ``True`` / ``"all"`` for every
+        point, default none. Returns ``pairs`` (the list), ``pair_cov`` (one dim(a) x dim(b) array per pair),
+        ``point_idx`` / ``point_cov`` (k, 3, 3), ``full`` ((6 nac + 4)^2, ordered as ``reduced_system``) when asked,
+        ``ac_cam`` and the fields of ``ba_cov_info`` (status, n, nac, pivot_min, pivot_max, cost, variance_factor,
+        time_*_ms). Units: the cost's (the residuals carry the 1/N weights); the variance factor is not applied."""
+        i32p = C.POINTER(C.c_int32)
+        adm = np.asarray(prob.obs_depth) > 1e-15
+        has = np.zeros(prob.n_cams, bool)
+        has[np.asarray(prob.obs_cam)[adm]] = True
+        if 0 <= prob.fixed_cam < prob.n_cams:
+            has[prob.fixed_cam] = False
+        ac_cam = np.nonzero(has)[0].astype(np.int32)
+        if pairs is None:
+            pairs = [(int(c), int(c)) for c in ac_cam] + [(COV_INTR, COV_INTR)]
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        pa = np.ascontiguousarray([a for a, _ in pairs], dtype=np.int32)
+        pb = np.ascontiguousarray([b for _, b in pairs], dtype=np.int32)
+        pc = np.zeros((len(pairs), 36))
+        if points is None or points is False:
+            pidx = np.zeros(0, dtype=np.int32)
+        elif points is True or (isinstance(points, str) and points == "all"):
+            pidx = np.arange(prob.n_points, dtype=np.int32)
+        else:
+            pidx = np.ascontiguousarray(points, dtype=np.int32)
+        ptc = np.zeros((len(pidx), 3, 3))
+        req, info = BaCovRequest(), BaCovInfo()
+        req.n_pairs = len(pairs)
+        if len(pairs):
+            req.pair_a, req.pair_b, req.pair_cov = pa.ctypes.data_as(i32p), pb.ctypes.data_as(i32p), _dptr(pc)
+        req.n_points = len(pidx)
+        if len(pidx):
+            req.point_idx, req.point_cov = pidx.ctypes.data_as(i32p), _dptr(ptc)
+        nfull = 6 * len(ac_cam) + 4
+        fm = np.zeros((nfull, nfull)) if full else None
+        if full:
+            req.full = _dptr(fm)
+        req.min_reciprocal_condition_number = float(min_rcond)
+        ps = prob.struct()
+        self._check(self._L.ba_covariance(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_covariance")
+        assert not full or info.n == nfull, (info.n, nfull)
+        dim = lambda v: 4 if v == COV_INTR else 6
+        out = dict(pairs=pairs, pair_cov=[pc[k, : dim(a) * dim(b)].reshape(dim(a), dim(b)).copy()
+                                          for k, (a, b) in enumerate(pairs)],
+                   point_idx=pidx, point_cov=ptc, ac_cam=ac_cam)
+        if full:
+            out["full"] = fm
+        out.update(info.as_dict())
+        return out

@@ -46,7 +46,8 @@ extern "C" {
  *   2  ba_summary and ba_prepare_info lead with `struct_size`: the caller sets it to sizeof() of ITS struct
  *      (BA_SUMMARY_INIT / BA_PREPARE_INFO_INIT), the library writes only that many bytes (fields a newer
  *      library added past the caller's size stay untouched) and rejects a size below the *_MIN_SIZE of this
- *      version with BA_E_INVALID. */
+ *      version with BA_E_INVALID.
+ *   2, additive  ba_covariance with ba_cov_request / ba_cov_info (both sized structs); nothing else changed. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -274,6 +275,49 @@ typedef struct ba_kernel_stat {
 } ba_kernel_stat;
 int32_t ba_kernel_stats(const ba_context* ctx, ba_kernel_stat* out, int32_t max_n); /* returns count */
 void ba_reset_kernel_stats(ba_context* ctx);
+
+/* ---- covariance of the estimate (the counterpart of ceres::Covariance) ----
+ * Sigma = (J^T J)^-1 at prob's parameters, J the Jacobian the LM loop linearises with (sqrt(rho')-robustified, the
+ * IntrinsicsPrior rows included, the gauge camera's columns and the cameras / points without an admissible
+ * observation removed), in the tangent space of ba_debug_linearize: [upsilon(3), omega(3)] per camera applied as
+ * T*exp(delta), 3 per point, 4 for fx, fy, cx, cy. No damping, no Jacobi scaling in the result. The residuals carry
+ * the reference's 1/N weights, so Sigma is in the cost's units as Ceres' would be; ba_cov_info.variance_factor
+ * reports 2 cost / (3 N + 4 - (6 nac + 3 nap + 4)) (0 when the denominator is <= 0) and is NOT applied.
+ * Camera / intrinsics blocks are blocks of the inverse of the undamped reduced camera system (dense, on the device);
+ * a point's 3x3 marginal is V^-1 + T^T Sigma[cols, cols] T, T = E V^-1, over the point's cameras and the intrinsics.
+ * Behaves like the debug hooks: prepares the window (the plan cache applies) and evaluates at prob's parameters;
+ * prob is not modified, and a following ba_solve / ba_solve_prepared behaves as if the call had not happened.
+ * Blocks: a pair that involves the gauge camera is all zeros (a constant block); a camera or point without an
+ * admissible observation is not estimable, its blocks are NaN (return code still 0); (a,b) and (b,a) are exact
+ * transposes and a diagonal block is exactly symmetric. The system counts as rank deficient when a Cholesky pivot
+ * is <= 0 or not finite or pivot_min / pivot_max < min_reciprocal_condition_number: the call returns 0 with
+ * status = BA_COV_RANK_DEFICIENT and every requested output NaN. Contexts with landmark shards: BA_E_INVALID. */
+#define BA_COV_INTR (-1)            /* the intrinsics block in pair_a / pair_b */
+#define BA_COV_OK 0
+#define BA_COV_RANK_DEFICIENT 1
+typedef struct ba_cov_request {
+    int32_t struct_size;            /* BA_COV_REQUEST_INIT */
+    int32_t n_pairs;
+    const int32_t* pair_a;          /* camera index of the window, or BA_COV_INTR */
+    const int32_t* pair_b;
+    double* pair_cov;               /* [n_pairs*36]: block k at 36*k, row-major dim(a) x dim(b), the rest 0 */
+    int32_t n_points;               /* 0 = none */
+    const int32_t* point_idx;       /* NULL with n_points == prob->n_points: every point, in order */
+    double* point_cov;              /* [n_points*9] row-major 3x3 */
+    double* full;                   /* optional [(6*nac+4)^2] row-major, ordered as ba_debug_reduced_system */
+    double min_reciprocal_condition_number; /* <= 0: 1e-14, Ceres' Covariance::Options default */
+} ba_cov_request;
+typedef struct ba_cov_info {
+    int32_t struct_size, status, n, nac;
+    double pivot_min, pivot_max;    /* squared Cholesky diagonal of the Jacobi-scaled system */
+    double cost, variance_factor;
+    double time_build_ms, time_invert_ms, time_points_ms, time_total_ms;
+} ba_cov_info;
+#define BA_COV_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_cov_request))
+#define BA_COV_INFO_MIN_SIZE ((int32_t)sizeof(ba_cov_info))
+#define BA_COV_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_COV_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_covariance(ba_context* ctx, const ba_problem* prob, const ba_cov_request* req, ba_cov_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the

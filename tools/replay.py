@@ -2,7 +2,10 @@
 """Replay a captured window (.miba, written by libmiba under MIBA_DUMP_DIR) or a BAL problem on
 the GPU, optionally beside the CPU oracle, and print both summaries.
 
-    python tools/replay.py window_1234_000003.miba [--oracle] [--iters N] [--no-depth]
+    python tools/replay.py window_1234_000003.miba [--oracle] [--iters N] [--no-depth] [--covariance]
+
+--covariance: after the solve, ba_covariance at the solved parameters; prints the per-camera sigma of translation and
+rotation (the tangent space [upsilon, omega] of T*exp(delta); cost units, the variance factor reported, not applied).
 """
 import argparse
 import json
@@ -23,6 +26,8 @@ def main():
     ap.add_argument("--oracle", action="store_true", help="also solve on the CPU oracle and compare final costs")
     ap.add_argument("--iters", type=int, default=None, help="override max_num_iterations")
     ap.add_argument("--no-depth", action="store_true", help="weight_unpr = 0 (e.g. BAL problems)")
+    ap.add_argument("--covariance", action="store_true",
+                    help="covariance of the solved window: per-camera sigma of translation and rotation")
     ap.add_argument("--out", default=None, help="write the solved window to this .miba file")
     a = ap.parse_args()
     from miba import problem_io
@@ -39,7 +44,17 @@ def main():
     q = prob.copy()
     with Solver(opts) as s:
         sg = s.solve(q)
+        cov = s.covariance(q) if a.covariance else None
     res["gpu"] = {k: sg[k] for k in KEYS}
+    if cov is not None:
+        import numpy as np
+        res["covariance"] = {k: cov[k] for k in ("status", "n", "nac", "pivot_min", "pivot_max", "cost",
+                                                 "variance_factor", "time_build_ms", "time_invert_ms", "time_total_ms")}
+        res["covariance"]["sigma_intrinsics"] = np.sqrt(np.diag(cov["pair_cov"][-1])).tolist()
+        # |sigma| of the translation part (upsilon) and of the rotation part (omega, radians) per active camera
+        res["covariance"]["cameras"] = [
+            {"cam": int(c), "sigma_t": float(np.sqrt(np.trace(b[:3, :3]))), "sigma_r": float(np.sqrt(np.trace(b[3:, 3:])))}
+            for c, b in zip(cov["ac_cam"], cov["pair_cov"])]
     if a.oracle:
         from oracle import oracle
         o = oracle.default_options()
