@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "ba_comm.h"
+#include "ba_dense.h"
 #include "ba_device.h"
 
 namespace miba {
@@ -114,7 +115,7 @@ struct DevProblem {
     int part_stride;
     int band_w;  // 16x16 tiles below the diagonal in the camera band; <=0 or >6: dense envelope kernel
     int cam_band;  // max over active cameras of (camera - first co-visible camera)
-    int solver;    // 0 dense envelope, 1 band, 2 block cyclic reduction
+    int solver;    // 0 dense envelope, 1 band, 2 block cyclic reduction, 3 blocked multi-workgroup Cholesky
     int rank, nranks;  // landmark shard of this context (ba_comm_init); rank 0 adds the camera/intrinsics terms
     int xcd_map;       // camera-side workgroups take the sub-segments by XCD band (xcd_seg, ba_kernels.hip)
 };
@@ -375,18 +376,24 @@ struct DevWork {
     // buffers, an unwritten value holding BCR_Y_EMPTY; the solve workgroup empties the other buffer (read by the
     // previous launch) for the next launch, launch_reset empties both at a solve's start
     double* tail_y = nullptr;
+    // the blocked multi-workgroup Cholesky (P.solver == 3, ba_dense.hip): its packed copy of the envelope and
+    // the block lists
+    DenseWork dense;
 };
 
 // kernel ids for per-launch HIP-event profiling (ba_kernel_stats)
 enum KernelId {
     K_CAM_SIDE = 0, K_LIN_FINALIZE, K_POINT_COLNORM, K_SCALE, K_MEMSET_S, K_ASSEMBLE, K_POINT_PREP, K_SCHUR_TILE,
     K_OBS_PAIRS, K_CHOL, K_UPDATE_CAMS, K_BACKSUB_EVAL, K_FINAL, K_DECIDE, K_XNORM, K_BCR_ELIM, K_BCR_CONTRIB,
-    K_BCR_BACK, K_BCR_BORDER, K_COMM, K_CAM_REDUCE, K_BCR_PERSIST, K_PP_REDUCE, K_DUMMY, K_LIN_POINT, K_COUNT
+    K_BCR_BACK, K_BCR_BORDER, K_COMM, K_CAM_REDUCE, K_BCR_PERSIST, K_PP_REDUCE, K_DUMMY, K_LIN_POINT,
+    K_DENSE_COPY, K_DENSE_DIAG, K_DENSE_PANEL, K_DENSE_TRAIL, K_DENSE_BACK, K_COUNT
 };
+static_assert(K_COUNT <= 32, "ba_options.profile_mask has one bit per kernel id");
 static const char* const kKernelNames[K_COUNT] = {
     "cam_side", "lin_finalize", "point_colnorm", "scale", "memset_S", "assemble", "point_prep", "schur_tile",
     "obs_pairs", "chol", "update_cams", "backsub_eval", "final", "lm_decide", "xnorm", "bcr_elim", "bcr_contrib",
-    "bcr_back", "bcr_border", "comm", "cam_reduce", "bcr_persist", "pp_reduce", "dummy", "lin_point"};
+    "bcr_back", "bcr_border", "comm", "cam_reduce", "bcr_persist", "pp_reduce", "dummy", "lin_point",
+    "dense_copy", "dense_diag", "dense_panel", "dense_trail", "dense_back"};
 
 // Records an event pair around each launch on the launch stream.
 struct Prof {

@@ -2766,6 +2766,7 @@ static hipError_t launch_band(const DevProblem& P, DevWork& W, hipStream_t s, Pr
 hipError_t launch_factor(const DevProblem& P, const BaConsts& c, DevWork& W, hipStream_t s, Prof* pf) {
     if (P.solver == 2 && W.tail) return hipSuccess;  // the band solve runs in launch_update's tail launch
     if (P.solver == 2) return launch_bcr(P, c, W, W.bcr, s, pf);  // k_bcr_border also applies the camera step
+    if (P.solver == 3) return launch_dense(W.st, W.S, P.npad, W.rhs, W.chol_flag, W.dense, s, pf);
     if (P.solver == 1) switch (P.band_w) {
         case 1: return launch_band<1>(P, W, s, pf);
         case 2: return launch_band<2>(P, W, s, pf);

@@ -70,6 +70,9 @@ enum BufId {
     // ba_covariance (allocated on its first call): the two dense work matrices, the points' W_o scratch, the
     // request's index lists + the status word, and the outputs
     B_COV_A, B_COV_Z, B_COV_W, B_COV_IDX, B_COV_OUT,
+    // the blocked multi-workgroup Cholesky (BA_LS_BLOCKED): packed envelope blocks, diagonal inverses, padded rhs
+    // and the block lists
+    B_DENSE_A, B_DENSE_Z, B_DENSE_B, B_DENSE_IDX,
     B_COUNT
 };
 
@@ -91,6 +94,8 @@ struct ba_context {
     // original obs index)
     Plan plan;
     std::vector<int> pt_idx, ac_cam;
+    DensePlan dplan;             // BA_LS_BLOCKED: the envelope at 64-block granularity, kept with the plan
+    std::vector<int> dplan_idx;  // its device index buffer's host image (outlives the upload)
     char* stage = nullptr;  // pinned staging of ba_prepare's uploads: [raw observations | plan index arrays]
     size_t stage_cap = 0;
     char* pstage = nullptr;  // pinned staging of the parameter uploads (cameras | points | intrinsics | prior)
@@ -646,7 +651,7 @@ static unsigned long long env_key() {
     static const char* const names[] = {"MIBA_OBS32", "MIBA_TILE_PTS", "MIBA_SUBSEG", "MIBA_SOLVER", "MIBA_DENSE_CHOL",
                                         "MIBA_BCR", "MIBA_XCD_MAP", "MIBA_FUSED", "MIBA_SW", "MIBA_FPL",
                                         "MIBA_BCR_DENSE1", "MIBA_PP_LANES", "MIBA_DEVICE_PLAN", "MIBA_TAIL",
-                                        "MIBA_BCR_BAND", "MIBA_BCR_XMAP"};
+                                        "MIBA_BCR_BAND", "MIBA_BCR_XMAP", "MIBA_BLOCKED_MIN"};
     unsigned long long h = 1469598103934665603ull;
     for (const char* n : names) {
         const char* v = std::getenv(n);
@@ -1258,8 +1263,16 @@ static int prepare_core(ba_context* ctx, const ba_problem* p, bool force_det) {
         // else the dense envelope kernel.
         const int bcr_nblk = (nac + BCR_CAMS - 1) / BCR_CAMS;
         P.solver = (cam_band < BCR_CAMS && bcr_nblk >= 1) ? 2 : (P.band_w > 0 ? 1 : 0);
+        // wide windows (no narrow band: global BA, loop closures): from npad >= BLOCKED_MIN_NPAD the blocked
+        // multi-workgroup Cholesky (ba_dense.hip) instead of the one-workgroup envelope kernel
+        {
+            long long bmin = BLOCKED_MIN_NPAD;
+            if (const char* e = std::getenv("MIBA_BLOCKED_MIN")) bmin = std::atoll(e);
+            if (P.solver == 0 && npad >= bmin) P.solver = 3;
+        }
         if (const char* e = std::getenv("MIBA_SOLVER")) {
             if (!std::strcmp(e, "dense")) P.solver = 0;
+            else if (!std::strcmp(e, "blocked")) P.solver = 3;
             else if (!std::strcmp(e, "band") && P.band_w > 0) P.solver = 1;
             else if (!std::strcmp(e, "bcr") && cam_band < BCR_CAMS && bcr_nblk >= 1) P.solver = 2;
         }
@@ -1301,6 +1314,35 @@ static int prepare_core(ba_context* ctx, const ba_problem* p, bool force_det) {
             Bw.bk = Bw.F2 + b64;
             Bw.flags = reinterpret_cast<unsigned*>(Bw.bk + 16);  // zeroed with the workspace above
             if (int rc = bcr_setup(ctx)) return rc;
+        }
+        if (P.solver == 3) {
+            DensePlan& dp = ctx->dplan;
+            dense_plan(pl.fcol, npad, dp);
+            std::vector<int>& h = ctx->dplan_idx;
+            h.clear();
+            const size_t o_bf = 0, o_rs = o_bf + dp.bfcol.size(), o_cp = o_rs + dp.rowstart.size(),
+                         o_cr = o_cp + dp.crptr.size();
+            size_t o_bk = o_cr + dp.crows.size();
+            o_bk += o_bk & 1;  // int2 alignment
+            h.insert(h.end(), dp.bfcol.begin(), dp.bfcol.end());
+            h.insert(h.end(), dp.rowstart.begin(), dp.rowstart.end());
+            h.insert(h.end(), dp.crptr.begin(), dp.crptr.end());
+            h.insert(h.end(), dp.crows.begin(), dp.crows.end());
+            h.resize(o_bk, 0);
+            h.insert(h.end(), dp.blk.begin(), dp.blk.end());
+            HIPCHECK(ctx, upload(ctx, B_DENSE_IDX, h.data(), h.size()));
+            HIPCHECK(ctx, ctx->buf[B_DENSE_A].ensure(sizeof(double) * DENSE_BB * (size_t)dp.n_env()));
+            HIPCHECK(ctx, ctx->buf[B_DENSE_Z].ensure(sizeof(double) * DENSE_BB * (size_t)dp.nblk));
+            HIPCHECK(ctx, ctx->buf[B_DENSE_B].ensure(sizeof(double) * DENSE_B * (size_t)dp.nblk));
+            DenseWork& D = ctx->W.dense;
+            const int* base = ctx->buf[B_DENSE_IDX].as<int>();
+            D.A = ctx->buf[B_DENSE_A].as<double>();
+            D.Zd = ctx->buf[B_DENSE_Z].as<double>();
+            D.bz = ctx->buf[B_DENSE_B].as<double>();
+            D.bfcol = base + o_bf; D.rowstart = base + o_rs; D.crptr = base + o_cp; D.crows = base + o_cr;
+            D.blk = reinterpret_cast<const int2*>(base + o_bk);
+            D.nblk = dp.nblk; D.n_env = dp.n_env();
+            D.h_crptr = dp.crptr.data();
         }
         fmark("solver_setup");
         DevWork& W = ctx->W;
@@ -1419,6 +1461,25 @@ static int prepare_core(ba_context* ctx, const ba_problem* p, bool force_det) {
             for (int k = 0; k < nb; ++k) {
                 const double r = pl.rptr[k + 1] - pl.rptr[k];
                 kf[K_CHOL] += (r * (r + 1) / 2) * 2.0 * 16 * 16 * 16 + r * 16 * 16 * 16 + 16 * 16 * 16 / 3.0;
+            }
+            if (P.solver == 3) {
+                // blocked Cholesky: per launch = the solve's total / its launches. A 64^3 block product is
+                // 2 * 64^3 flops and moves three blocks; the diagonal block is factored and inverted (2 * 64^3 / 3)
+                const DensePlan& dp = ctx->dplan;
+                const double blk = 64.0 * 64 * 8, f3 = 2.0 * 64 * 64 * 64;
+                double n_pan = 0, n_tr = 0, n_lp = 0;
+                for (int k = 0; k < dp.nblk; ++k) {
+                    const double r = dp.crptr[k + 1] - dp.crptr[k];
+                    n_pan += r;
+                    n_tr += r * (r + 1) / 2;
+                    n_lp += r > 0 ? 1 : 0;
+                }
+                n_lp = std::max(n_lp, 1.0);
+                kb[K_DENSE_COPY] = 2.0 * dp.n_env() * blk + 2.0 * npad * 8;
+                kb[K_DENSE_DIAG] = 2 * blk + 2 * 64 * 8.0; kf[K_DENSE_DIAG] = f3 / 3 + 64.0 * 64;
+                kb[K_DENSE_PANEL] = n_pan * 3 * blk / n_lp; kf[K_DENSE_PANEL] = n_pan * f3 / n_lp;
+                kb[K_DENSE_TRAIL] = (n_tr * 4 + n_pan) * blk / n_lp; kf[K_DENSE_TRAIL] = (n_tr * f3 + n_pan * 2 * 64 * 64) / n_lp;
+                kb[K_DENSE_BACK] = (n_pan + dp.nblk) * blk / dp.nblk; kf[K_DENSE_BACK] = (n_pan + dp.nblk) * 2.0 * 64 * 64 / dp.nblk;
             }
             if (P.solver == 2) {
                 // block cyclic reduction: per eliminated 64-dof block, Cholesky 64^3/3 + forward solve of
@@ -1652,6 +1713,9 @@ static int enqueue_reset(ba_context* ctx, const LmState& st0, int n_cams) {
     const int max_iter = std::max(ctx->opts.max_num_iterations, 0);
     HIPCHECK(ctx, ctx->buf[B_LOG].ensure(sizeof(double) * LOG_W * (max_iter + 2)));
     W.log = ctx->buf[B_LOG].as<double>();
+    // (a terminal row's gradient entry and every row's last entry are never written by the decision: they read
+    // as zero, not as whatever the allocation held)
+    HIPCHECK(ctx, hipMemsetAsync(W.log, 0, sizeof(double) * LOG_W * (max_iter + 2), ctx->stream));
     // the split BCR kernel's flags hold 4 * epoch + panel (one epoch per launch): re-initialise the hand-off
     // state long before 4 * epoch wraps (2^30 launches) on a context that re-solves one prepared window forever
     if (P.solver == 2 && ctx->bcr_launches > (1ull << 28))
@@ -1758,6 +1822,9 @@ static int32_t solve_prepared(ba_context* ctx, ba_problem* p, ba_summary* sum, d
     // Iterations enqueued after the termination are no-ops (their kernels exit at once).
     int launched = 0;
     int batch = 2;
+    // (profiled: the blocked Cholesky's launches of one batch fit the event pool)
+    const int batch_cap = P.solver == 3 ? std::max(1, std::min(8, Prof::MAXP / (4 * W.dense.nblk + 16))) : 8;
+    batch = std::min(batch, batch_cap);
     int retries = 0;  // decisions that re-ran an iteration after a BCR hand-off timeout (not LM iterations)
     LmState& S = h_state;
     const bool shard = W.comm.on();
@@ -1841,7 +1908,7 @@ static int32_t solve_prepared(ba_context* ctx, ba_problem* p, ba_summary* sum, d
             continue;
         }
         if (S.done || launched > launch_cap()) break;
-        batch = std::min(batch * 2, 8);
+        batch = std::min(batch * 2, batch_cap);
     }
     if (!S.done || S.msg == MSG_TIMEOUT) {  // cannot happen (max_iter bounds the loop; timeouts are re-run)
         ctx->err = "LM loop did not terminate";
@@ -1892,7 +1959,8 @@ static int32_t solve_prepared(ba_context* ctx, ba_problem* p, ba_summary* sum, d
     auto dk = [&](int k) { return ctx->k_ms[k] - kms0[k]; };
     sum->time_linearize_ms = dk(K_CAM_SIDE) + dk(K_LIN_FINALIZE) + dk(K_POINT_COLNORM) + dk(K_SCALE);
     sum->time_schur_ms = dk(K_MEMSET_S) + dk(K_ASSEMBLE) + dk(K_POINT_PREP) + dk(K_SCHUR_TILE) + dk(K_OBS_PAIRS);
-    sum->time_factor_ms = dk(K_CHOL) + dk(K_BCR_ELIM) + dk(K_BCR_CONTRIB) + dk(K_BCR_BACK) + dk(K_BCR_BORDER);
+    sum->time_factor_ms = dk(K_CHOL) + dk(K_BCR_ELIM) + dk(K_BCR_CONTRIB) + dk(K_BCR_BACK) + dk(K_BCR_BORDER) +
+                          dk(K_DENSE_COPY) + dk(K_DENSE_DIAG) + dk(K_DENSE_PANEL) + dk(K_DENSE_TRAIL) + dk(K_DENSE_BACK);
     sum->time_update_ms = dk(K_UPDATE_CAMS) + dk(K_BACKSUB_EVAL) + dk(K_FINAL) + dk(K_DECIDE);
     return BA_OK;
 }

@@ -23,6 +23,8 @@ BA_NO_CONVERGENCE = 1
 BA_FAILURE = 2
 
 TERMINATION_NAMES = {0: "CONVERGENCE", 1: "NO_CONVERGENCE", 2: "FAILURE"}
+# ba_summary.linear_solver (BA_LS_*): the reduced-solve path; the names are MIBA_SOLVER's values
+LINEAR_SOLVER_NAMES = {0: "dense", 1: "band", 2: "bcr", 3: "blocked"}
 
 # columns of an iteration-log row (ba_iteration_log, ba_debug_step), BA_LOG_WIDTH = 8 with the last one unused
 LOG_FIELDS = ("cost", "cost_change", "gradient_max_norm", "step_norm", "tr_ratio", "tr_radius", "accepted")
@@ -122,6 +124,7 @@ class BaSummary(C.Structure):
              if name not in ("message", "struct_size", "reserved0")}
         d["message"] = self.message.decode(errors="replace")
         d["termination"] = TERMINATION_NAMES.get(self.termination_type, str(self.termination_type))
+        d["linear_solver_name"] = LINEAR_SOLVER_NAMES.get(self.linear_solver, str(self.linear_solver))
         return d
 
 

@@ -178,8 +178,8 @@ class Solver:
         """The production LM step of the window's first iteration (ba_debug_step), on the paths the prepare
         chose: ac_cam (nac,), delta_cam (nac, 6), delta_intr (4,), delta_pts (n_points, 3) in parameter space,
         row 1 of the iteration log by name (LOG_FIELDS, ``accepted`` as int), the factorisation ``flag``,
-        ``retried``, and the window's ``linear_solver``, ``camera_band``, ``band_tiles`` (banded Cholesky only) and
-        ``num_iterations``. ``prob`` is not modified."""
+        ``retried``, and the window's ``linear_solver`` (capi.LINEAR_SOLVER_NAMES: 0 dense, 1 band, 2 bcr, 3 blocked),
+        ``camera_band``, ``band_tiles`` (banded Cholesky only) and ``num_iterations``. ``prob`` is not modified."""
         ps = prob.struct()
         nc = max(prob.n_cams, 1)
         ac = np.zeros(nc, dtype=np.int32); dc = np.zeros((nc, 6)); dk = np.zeros(4)

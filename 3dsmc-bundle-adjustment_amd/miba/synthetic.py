@@ -218,3 +218,92 @@ def make_landmark_shard(name: str, shard: int, **overrides) -> ProblemArrays:
     cfg["seed"] = base + 1009 * shard
     cfg["cam_seed"] = base
     return make_problem(**cfg)
+
+
+def _trajectory_at(t: np.ndarray):
+    """make_problem's curve (_trajectory) at the real-valued frame positions ``t``."""
+    t = np.asarray(t, dtype=np.float64)
+    n = len(t)
+    pos = np.stack([0.01 * t, 0.04 * np.sin(t / 35.0), 0.03 * np.sin(t / 50.0 + 0.5)], axis=1)
+    yaw = 0.3 * np.sin(t / 60.0)
+    pitch = 0.15 * np.sin(t / 45.0 + 1.0)
+    cy, sy, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
+    Ry = np.zeros((n, 3, 3))
+    Ry[:, 0, 0], Ry[:, 0, 2], Ry[:, 1, 1], Ry[:, 2, 0], Ry[:, 2, 2] = cy, sy, 1.0, -sy, cy
+    Rx = np.zeros((n, 3, 3))
+    Rx[:, 0, 0], Rx[:, 1, 1], Rx[:, 1, 2], Rx[:, 2, 1], Rx[:, 2, 2] = 1.0, cp, -sp, sp, cp
+    return Ry @ Rx, pos
+
+
+def make_sweep_problem(n_cams: int, n_points: int, obs_per_pass: int = 5, passes: int = 2, seed: int = 0,
+                       pixel_noise: float = 0.5, outlier_frac: float = 0.02, outlier_px: float = 20.0,
+                       depth_noise: float = 0.01, rot_noise: float = 0.01, trans_noise: float = 0.01,
+                       point_noise: float = 0.02, intr_offset=(2.0, -1.5, 1.0, -0.8), fixed_cam: int = 0,
+                       sensor_f32: bool = False) -> ProblemArrays:
+    """A window whose co-visibility is not a narrow band (a hand-held sweep over one scene, TUM fr1/xyz-like; a
+    loop closure): the cameras sweep make_problem's curve ``passes`` times, ``n_cams / passes`` keyframes per
+    sweep; every sweep starts over at the start of the curve (the way back is not keyframed), a fraction of a
+    frame further along, so no two cameras coincide. A point is seen by ``obs_per_pass`` consecutive cameras around
+    its birth position on EVERY sweep: its track spans ``n_cams / passes * (passes - 1) + obs_per_pass`` cameras,
+    the camera band of the reduced system is about ``n_cams * (1 - 1 / passes)``, and every point is an overflow
+    point of the Schur tiles. Noise, outliers, float32 sensor values, the gauge camera and the behind-the-camera
+    check are make_problem's."""
+    passes, opp = int(passes), int(obs_per_pass)
+    if passes < 1 or n_cams % passes:
+        raise ValueError("n_cams must be a multiple of passes")
+    m = n_cams // passes  # keyframes per sweep
+    opp = min(opp, m)
+    rng = np.random.default_rng(seed)
+    cam_pass, cam_pos = np.divmod(np.arange(n_cams), m)
+    R_wc, t_wc = _trajectory_at(cam_pos + cam_pass / passes)
+    K_true = ROS_DEFAULT_INTRINSICS + np.asarray(intr_offset, dtype=np.float64)
+    # the first position of a point's run spreads the points evenly over the sweep
+    start = np.minimum(np.floor(np.arange(n_points) * (m - opp + 1) / max(n_points, 1)).astype(np.int64), m - opp)
+    birth = start + opp // 2  # (a camera of the first sweep)
+    u = rng.uniform(60, IMAGE_W - 60, n_points)
+    v = rng.uniform(50, IMAGE_H - 50, n_points)
+    z = rng.uniform(0.8, 4.0, n_points)
+    pc = np.stack([(u - K_true[2]) / K_true[0] * z, (v - K_true[3]) / K_true[1] * z, z], axis=1)
+    X = np.einsum("nij,nj->ni", R_wc[birth], pc) + t_wc[birth]
+    per_pt = passes * opp
+    n_obs = n_points * per_pt
+    obs_pt = np.repeat(np.arange(n_points, dtype=np.int64), per_pt)
+    within = np.tile(np.arange(per_pt), n_points)
+    obs_cam = (within // opp) * m + np.repeat(start, per_pt) + within % opp
+    d = X[obs_pt] - t_wc[obs_cam]
+    p_c = np.einsum("nji,nj->ni", R_wc[obs_cam], d)  # R^T (X - t)
+    zc = p_c[:, 2]
+    if np.any(zc <= 0.05):
+        raise RuntimeError("synthetic generator produced a point behind a camera")
+    uv = np.stack([K_true[0] * p_c[:, 0] / zc + K_true[2], K_true[1] * p_c[:, 1] / zc + K_true[3]], axis=1)
+    uv += rng.normal(0.0, pixel_noise, uv.shape)
+    out = rng.random(n_obs) < outlier_frac
+    uv[out] += rng.uniform(-outlier_px, outlier_px, (int(out.sum()), 2))
+    depth = zc * (1.0 + rng.normal(0.0, depth_noise, n_obs))
+    dR = _rodrigues(rng.normal(0.0, rot_noise, (n_cams, 3)))
+    R0 = R_wc @ dR
+    t0 = t_wc + rng.normal(0.0, trans_noise, (n_cams, 3))
+    if 0 <= fixed_cam < n_cams:
+        R0[fixed_cam] = R_wc[fixed_cam]
+        t0[fixed_cam] = t_wc[fixed_cam]
+    cams = np.concatenate([quat_from_rotmat(R0), t0], axis=1)
+    pts0 = X + rng.normal(0.0, point_noise, X.shape)
+    if sensor_f32:
+        uv = uv.astype(np.float32).astype(np.float64)
+        depth = depth.astype(np.float32).astype(np.float64)
+    truth = dict(cams=np.concatenate([quat_from_rotmat(R_wc), t_wc], axis=1), points=X, intr=K_true)
+    return ProblemArrays(cams, pts0, ROS_DEFAULT_INTRINSICS.copy(), ROS_DEFAULT_INTRINSICS.copy(), obs_cam, obs_pt,
+                         uv, depth, fixed_cam, meta=dict(truth=truth, seed=seed))
+
+
+# wide windows of tools/wide_bench.py (DESIGN §4.9): global BA of 200 / 50 keyframes swept twice
+SWEEP_CONFIGS = {
+    "G1": dict(n_cams=200, n_points=100000, obs_per_pass=5, passes=2, seed=11),
+    "G2": dict(n_cams=50, n_points=4000, obs_per_pass=5, passes=2, seed=12),
+}
+
+
+def make_sweep_config(name: str, **overrides) -> ProblemArrays:
+    cfg = dict(SWEEP_CONFIGS[name], sensor_f32=True)
+    cfg.update(overrides)
+    return make_sweep_problem(**cfg)

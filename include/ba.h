@@ -47,7 +47,9 @@ extern "C" {
  *      (BA_SUMMARY_INIT / BA_PREPARE_INFO_INIT), the library writes only that many bytes (fields a newer
  *      library added past the caller's size stay untouched) and rejects a size below the *_MIN_SIZE of this
  *      version with BA_E_INVALID.
- *   2, additive  ba_covariance with ba_cov_request / ba_cov_info (both sized structs); nothing else changed. */
+ *   2, additive  ba_covariance with ba_cov_request / ba_cov_info (both sized structs); nothing else changed.
+ *   2, additive  BA_LS_BLOCKED, a fourth value of ba_summary.linear_solver (wide co-visibility windows); no struct
+ *                changed. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -135,6 +137,7 @@ typedef struct ba_problem {
 #define BA_LS_DENSE 0 /* dense-envelope LDS Cholesky */
 #define BA_LS_BAND 1  /* banded LDS Cholesky (6x6 block band <= 6) */
 #define BA_LS_BCR 2   /* block cyclic reduction over 64-dof camera blocks */
+#define BA_LS_BLOCKED 3 /* multi-workgroup blocked Cholesky over 64-column blocks (wide co-visibility windows) */
 
 typedef struct ba_summary {
     int32_t struct_size;            /* in: sizeof(ba_summary) of the caller's header (BA_SUMMARY_INIT) */
@@ -149,7 +152,7 @@ typedef struct ba_summary {
     int32_t num_active_cams;
     int32_t num_active_points;
     int32_t reduced_system_size;    /* 6*active_cams + 4 */
-    int32_t linear_solver;          /* reduced-system solver used: BA_LS_DENSE / _BAND / _BCR */
+    int32_t linear_solver;          /* reduced-system solver used: BA_LS_DENSE / _BAND / _BCR / _BLOCKED */
     int32_t camera_band;            /* max |cam_a - cam_b| over coupled active cameras */
     double time_setup_ms;           /* host prep + H2D + structure build */
     double time_lm_ms;              /* LM loop wall time (device work + host control) */

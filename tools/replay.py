@@ -17,7 +17,8 @@ sys.path.insert(0, os.path.join(ROOT, "3dsmc-bundle-adjustment_amd"))
 sys.path.insert(0, ROOT)
 
 KEYS = ("initial_cost", "final_cost", "num_iterations", "num_successful_steps", "num_unsuccessful_steps",
-        "termination", "num_obs_admissible", "reduced_system_size", "linear_solver", "time_setup_ms", "time_lm_ms")
+        "termination", "num_obs_admissible", "reduced_system_size", "linear_solver", "linear_solver_name", "time_setup_ms",
+        "time_lm_ms")
 
 
 def main():
