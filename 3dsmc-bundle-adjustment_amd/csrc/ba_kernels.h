@@ -243,6 +243,14 @@ __device__ __forceinline__ void update_camera(const DevProblem& P, const BaConst
     load_cam_step_ops(P, cur, scale, camdata, t, o);
     cam_step(P, c, cur, radius, o, t, yv, delta, acc);
 }
+// x + d rounded on its own, never contracted with the product that made d: hipcc fuses K + (-y s) into one FMA
+// (v_fma_f64) while delta holds the rounded product, so the stored candidate and x + the stored step differed by an ulp
+// of K in a few percent of the steps; with this the candidate slot is K + delta bitwise on every path, and the band
+// tail's own K (cand_compute) is the value intr_step stores whatever either instantiation would have fused.
+__device__ __forceinline__ double add_step(double x, double d) {
+#pragma clang fp contract(off)
+    return x + d;
+}
 // The intrinsics' step operands (update_intrinsics) and the step from them.
 struct IntrStepOps {
     double K[4], sk[4], uk[4], gk[4], prior[4];  // K, Jacobi scale, diag of the prior-augmented Ukk, gk, prior
@@ -267,7 +275,7 @@ __device__ __forceinline__ void intr_step(const DevProblem& P, const BaConsts& c
         const double sk = o.sk[m], ym = yk4[m];
         const double dk = -ym * sk;
         st_opt<PUB>(delta + P.kb + m, dk);
-        const double kn = o.K[m] + dk;
+        const double kn = add_step(o.K[m], dk);
         st_opt<PUB>(Kn + m, kn);
         const double df = o.K[m] - kn;
         acc[0] += df * df;

@@ -134,6 +134,7 @@ struct ba_context {
     bool tail_possible = false;  // the window's LM loop can take the band tail launch (set before bcr_setup)
     int prep_nc = -1, prep_np = -1, prep_no = -1;
     int last_iter = -1;        // iterations of the last solve (ba_iteration_log rows - 1)
+    int dbg_step_base = -1;    // ba_debug_step's slot of x while the device still holds what that step left behind
     // shard_min_obs: a window below the threshold is gathered onto every rank and solved there alone; the
     // communicator is parked meanwhile (restored by the next prepare), the rank's points are the slice
     // [gather_off, gather_off + its n_points) of the gathered window
@@ -495,6 +496,7 @@ static int shard_replicas_agree(ba_context* ctx, const ba_problem* p) {
 }
 
 static int prepare(ba_context* ctx, const ba_problem* p) {
+    ctx->dbg_step_base = -1;  // (every entry point that rewrites the device state prepares or resets first)
     if (ctx->comm_parked.on()) {  // the last window ran gathered: the communicator is back for this one
         ctx->W.comm = ctx->comm_parked;
         ctx->comm_parked = Comm{};
@@ -1710,6 +1712,7 @@ static LmParams lm_params(const ba_context* ctx) {
 static int enqueue_reset(ba_context* ctx, const LmState& st0, int n_cams) {
     DevProblem& P = ctx->P;
     DevWork& W = ctx->W;
+    ctx->dbg_step_base = -1;
     const int max_iter = std::max(ctx->opts.max_num_iterations, 0);
     HIPCHECK(ctx, ctx->buf[B_LOG].ensure(sizeof(double) * LOG_W * (max_iter + 2)));
     W.log = ctx->buf[B_LOG].as<double>();
@@ -2124,6 +2127,52 @@ extern "C" int32_t ba_debug_step(ba_context* ctx, const ba_problem* p, double ra
     std::copy(lg, lg + LOG_W, log_row);
     const int32_t inf[BA_STEP_INFO_N] = {cf, retried, P.solver, P.cam_band, P.solver == 1 ? P.band_w : 0, h_st.iter, 0, 0};
     std::copy(inf, inf + BA_STEP_INFO_N, info);
+    ctx->dbg_step_base = base;
+    return BA_OK;
+}
+
+extern "C" int32_t ba_debug_step_state(ba_context* ctx, double* cams_x, double* cams_cand, double* intr_x,
+                                       double* intr_cand, double* pts_x, double* pts_cand, double* scal, double* lin,
+                                       double* log_rows, double* state) {
+    if (!ctx) return BA_E_INVALID;
+    if (!cams_x || !cams_cand || !intr_x || !intr_cand || !pts_x || !pts_cand || !scal || !lin || !log_rows || !state) {
+        ctx->err = "ba_debug_step_state: null argument";
+        return BA_E_INVALID;
+    }
+    if (!ctx->prepared || ctx->dbg_step_base < 0) {
+        ctx->err = "ba_debug_step_state: no ba_debug_step on this context since the last prepare / solve";
+        return BA_E_INVALID;
+    }
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    DevProblem& P = ctx->P;
+    DevWork& W = ctx->W;
+    hipStream_t s = ctx->stream;
+    const int base = ctx->dbg_step_base;
+    const size_t nc7 = 7 * (size_t)ctx->prep_nc, np3 = 3 * (size_t)ctx->prep_np, off = 3 * (size_t)ctx->gather_off;
+    LmState st{};
+    double sc[SC_N] = {};
+    // copies only (pageable destinations: each returns once its data has arrived)
+    if (nc7) {
+        HIPCHECK(ctx, hipMemcpyAsync(cams_x, P.cams[base], sizeof(double) * nc7, hipMemcpyDeviceToHost, s));
+        HIPCHECK(ctx, hipMemcpyAsync(cams_cand, P.cams[base ^ 1], sizeof(double) * nc7, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(ctx, hipMemcpyAsync(intr_x, P.K[base], sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, hipMemcpyAsync(intr_cand, P.K[base ^ 1], sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+    if (np3) {
+        HIPCHECK(ctx, hipMemcpyAsync(pts_x, P.pts[base] + off, sizeof(double) * np3, hipMemcpyDeviceToHost, s));
+        HIPCHECK(ctx, hipMemcpyAsync(pts_cand, P.pts[base ^ 1] + off, sizeof(double) * np3, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(ctx, hipMemcpyAsync(sc, W.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, hipMemcpyAsync(lin, W.lin, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, hipMemcpyAsync(log_rows, W.log, sizeof(double) * 2 * LOG_W, hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, hipMemcpyAsync(&st, W.st, sizeof(LmState), hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, hipStreamSynchronize(s));
+    const double scv[BA_STEP_SCAL_N] = {sc[SC_MCC], sc[SC_CAND], sc[SC_SN2], sc[SC_GMAX_PT], sc[SC_BAD], sc[SC_XN2], 0, 0};
+    std::copy(scv, scv + BA_STEP_SCAL_N, scal);
+    const double stv[BA_STEP_STATE_N] = {st.radius, st.decrease_factor, st.xnorm2, st.x_cost, st.final_cost,
+                                         (double)st.cur, (double)st.termination, (double)st.msg,
+                                         st.gmax_ci, st.initial_cost, (double)st.iter, (double)base};
+    std::copy(stv, stv + BA_STEP_STATE_N, state);
     return BA_OK;
 }
 

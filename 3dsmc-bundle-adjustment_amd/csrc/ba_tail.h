@@ -446,7 +446,8 @@ __device__ __forceinline__ void cand_compute(const DevProblem& P, int cur, const
     if (threadIdx.x == TPB - 1) {  // intr_step's candidate: K + (-y_k s_k)
         double* const kc = CL + 8 * (size_t)P.n_cams;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) kc[m] = P.K[cur][m] + (-(YL ? y[P.kb + m] : tail_ld(y + P.kb + m)) * scale[P.off_k + m]);
+        for (int m = 0; m < 4; ++m)
+            kc[m] = add_step(P.K[cur][m], -(YL ? y[P.kb + m] : tail_ld(y + P.kb + m)) * scale[P.off_k + m]);
     }
 }
 

@@ -186,14 +186,45 @@ class Solver:
         dpt = np.zeros((prob.n_points, 3)); row = np.zeros(_lib.LOG_WIDTH)
         n = C.c_int32(0)
         info = np.zeros(8, dtype=np.int32)  # BA_STEP_INFO_N
+        self._step_dims = None
         self._check(self._L.ba_debug_step(self._h, C.byref(ps), radius, C.byref(n),
                                           ac.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(dc), _dptr(dk), _dptr(dpt),
                                           _dptr(row), info.ctypes.data_as(C.POINTER(C.c_int32))), "ba_debug_step")
+        self._step_dims = (prob.n_cams, prob.n_points)
         out = dict(ac_cam=ac[: n.value].copy(), delta_cam=dc[: n.value].copy(), delta_intr=dk, delta_pts=dpt,
                    flag=int(info[0]), retried=int(info[1]), linear_solver=int(info[2]), camera_band=int(info[3]),
                    band_tiles=int(info[4]), num_iterations=int(info[5]))
         out.update({k: float(v) for k, v in zip(LOG_FIELDS, row)})
         out["accepted"] = int(row[6])
+        return out
+
+    STEP_MSG_KINDS = ("none", "max_iter", "grad_tol", "min_radius", "param_tol", "func_tol", "invalid", "eval_fail",
+                      "timeout")
+
+    def lm_step_state(self) -> dict:
+        """What the last ``lm_step`` left on the device (ba_debug_step_state; no kernel runs): the
+        parameters the step was computed from and the candidate slot (``cams_x`` / ``cams_cand`` (n_cams, 7),
+        ``intr_x`` / ``intr_cand`` (4,), ``pts_x`` / ``pts_cand`` (n_points, 3), in the caller's order), the step
+        scalars ``mcc``, ``cand``, ``sn2``, ``gmax_pt``, ``bad``, ``xn2``, ``lin`` (cost at x, gradient max-norm of
+        cameras + intrinsics), ``log`` (rows 0 and 1 of the iteration log) and the LM state after the decision:
+        ``radius``, ``decrease_factor``, ``xnorm2``, ``x_cost``, ``final_cost``, ``cur``, ``termination``, ``msg``
+        (one of STEP_MSG_KINDS), ``gmax_ci``, ``initial_cost``, ``iter`` and ``base`` (the slot of x)."""
+        if getattr(self, "_step_dims", None) is None:
+            raise MibaError("lm_step_state: no lm_step on this solver")
+        n_cams, n_points = self._step_dims
+        nc, npt = max(n_cams, 1), max(n_points, 1)
+        cx = np.zeros((nc, 7)); cc = np.zeros((nc, 7)); kx = np.zeros(4); kc = np.zeros(4)
+        px = np.zeros((npt, 3)); pc = np.zeros((npt, 3))
+        scal = np.zeros(8); lin = np.zeros(2); log = np.zeros((2, _lib.LOG_WIDTH)); st = np.zeros(12)
+        self._check(self._L.ba_debug_step_state(self._h, _dptr(cx), _dptr(cc), _dptr(kx), _dptr(kc), _dptr(px),
+                                                _dptr(pc), _dptr(scal), _dptr(lin), _dptr(log), _dptr(st)),
+                    "ba_debug_step_state")
+        out = dict(cams_x=cx[:n_cams], cams_cand=cc[:n_cams], intr_x=kx, intr_cand=kc,
+                   pts_x=px[:n_points], pts_cand=pc[:n_points], lin=lin, log=log)
+        out.update({k: float(v) for k, v in zip(("mcc", "cand", "sn2", "gmax_pt", "bad", "xn2"), scal)})
+        out.update({k: float(v) for k, v in zip(("radius", "decrease_factor", "xnorm2", "x_cost", "final_cost"), st)})
+        out.update(cur=int(st[5]), termination=int(st[6]), msg=self.STEP_MSG_KINDS[int(st[7])], gmax_ci=float(st[8]),
+                   initial_cost=float(st[9]), iter=int(st[10]), base=int(st[11]))
         return out
 
     def camera_sums(self, prob: ProblemArrays):

@@ -371,6 +371,27 @@ int32_t ba_debug_camera_sums(ba_context* ctx, const ba_problem* prob, int32_t* n
 int32_t ba_debug_step(ba_context* ctx, const ba_problem* prob, double radius, int32_t* nac, int32_t* ac_cam,
                       double* delta_cam, double* delta_intr, double* delta_pts, double* log_row, int32_t* info);
 
+/* Test hook: what the last ba_debug_step left on the device, copied out without launching a kernel. Valid after a
+ * successful ba_debug_step on the same context and until its next prepare / solve (BA_E_INVALID otherwise). All
+ * outputs are required; cameras, intrinsics and points in the caller's order, as ba_debug_step was given them:
+ *   cams_x, cams_cand[n_cams*7]   the parameter slot the step was computed from and the candidate slot
+ *   intr_x, intr_cand[4]          (the gauge camera and blocks without an admissible observation hold the
+ *   pts_x, pts_cand[n_points*3]    prepared value in both slots)
+ *   scal[BA_STEP_SCAL_N]          the step scalars of that iteration: model cost change, candidate cost, ambient
+ *                                 |x - x_cand|^2, gradient max-norm over the points, the bad-step code, |x_cand|^2,
+ *                                 the rest 0
+ *   lin[2]                        cost at x, gradient max-norm over cameras + intrinsics
+ *   log_rows[2*BA_LOG_WIDTH]      rows 0 and 1 of the iteration log (row 0 carries the gradient max-norm at x)
+ *   state[BA_STEP_STATE_N]        the LM state after the decision: radius, decrease_factor, xnorm2, x_cost,
+ *                                 final_cost, cur (the slot of the accepted parameters), termination (-1 while
+ *                                 the solve goes on), msg (the message kind), gmax_ci, initial_cost, iter, and
+ *                                 the slot of x (so cur != that slot exactly when the step was accepted) */
+#define BA_STEP_SCAL_N 8
+#define BA_STEP_STATE_N 12
+int32_t ba_debug_step_state(ba_context* ctx, double* cams_x, double* cams_cand, double* intr_x, double* intr_cand,
+                            double* pts_x, double* pts_cand, double* scal, double* lin, double* log_rows,
+                            double* state);
+
 /* Test hook: FNV-1a digests of the last prepared window's plan arrays as the kernels read them from HBM (the
  * observation orderings, point order, tiles, chunks, segments, envelope), one per array, into out[max_n].
  * Returns the number of arrays. The host plan and the device plan (MIBA_DEVICE_PLAN) give the same digests. */
