@@ -952,10 +952,8 @@ static size_t band_lds_bytes(int bc, int nb, int nac) { return sizeof(double) * 
 
 // The band path for this window: cameras per block (1..3), 0 when it does not apply. mode: MIBA_BCR_BAND
 // (0 off, 2 also for one-block windows, else the default: windows of more than one 64-dof BCR block).
-int bcr_band_ok(int nac, int cam_band, int kb, bool one_block) {
-    if (nac < 2 || cam_band > 3 || std::getenv("MIBA_BCR")) return 0;
-    const char* e = std::getenv("MIBA_BCR_BAND");
-    const int mode = e ? std::atoi(e) : 1;
+int bcr_band_ok(int nac, int cam_band, int kb, bool one_block, bool bcr_set, int mode) {
+    if (nac < 2 || cam_band > 3 || bcr_set) return 0;
     if (mode == 0) return 0;
     // one BCR block: k_bcr_dense1, unless the band solve's tail launch will run (C1: 46.8-47.8 us per LM iteration
     // against 48.0-48.9 with k_bcr_dense1, same box) or MIBA_BCR_BAND=2

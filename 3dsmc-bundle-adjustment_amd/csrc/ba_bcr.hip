@@ -2531,10 +2531,9 @@ hipError_t bcr_set_spin_limit(unsigned limit) {
 }
 
 // One-block windows take k_bcr_dense1 (MIBA_BCR_DENSE1=0, or any MIBA_BCR path override, keeps the split kernel).
-int bcr_dense1_ok(int nblk, int kb) {
-    if (nblk != 1 || kb + 4 > BB || std::getenv("MIBA_BCR")) return 0;
-    const char* e = std::getenv("MIBA_BCR_DENSE1");
-    return (e && e[0] == '0') ? 0 : 1;
+int bcr_dense1_ok(int nblk, int kb, bool bcr_set, bool want) {
+    if (nblk != 1 || kb + 4 > BB || bcr_set) return 0;
+    return want ? 1 : 0;
 }
 
 int bcr_persist_ok(int nblk) {
@@ -2556,9 +2555,8 @@ int bcr_persist_ok(int nblk) {
 
 // MIBA_BCR_XMAP=1 (opt-in): k_bcr_split's workgroups on XCDs 0-3 only, when they all fit there at once (every
 // workgroup of the split kernel waits on others: a launch that does not fit would time out)
-int bcr_xmap_ok(int nblk, int persist) {
-    const char* e = std::getenv("MIBA_BCR_XMAP");
-    if (!(e && e[0] == '1') || persist < 2) return 0;
+int bcr_xmap_ok(int nblk, int persist, bool want) {
+    if (!want || persist < 2) return 0;
     int dev = 0, ncu = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;

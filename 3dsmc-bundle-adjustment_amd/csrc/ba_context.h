@@ -1,0 +1,195 @@
+// ba_context.h — the libmiba context and what its host translation units share (internal).
+//
+// ba_solver.cpp: the C-ABI surface and the LM loop; ba_prepare.cpp: ba_prepare's phases (staging, plan, device
+// structure, plan cache); ba_debug.cpp: the ba_debug_* entry points.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/ba.h"
+#include "ba_host.h"
+#include "ba_kernels.h"
+#include "ba_plan.h"
+#include "ba_settings.h"
+
+inline double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap && p) return hipSuccess;
+        if (p) hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = std::max<size_t>(bytes, 256);
+        hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// Pinned host memory, grown on demand (an eighth of slack, at least min_cap bytes) and kept by the context.
+// Growing keeps the first `keep` bytes; a mapped buffer is host-coherent and `dev` its device address. The caller
+// makes sure that no DMA still reads the buffer before it asks for more than `cap`.
+struct PinnedBuf {
+    size_t min_cap = 0;
+    bool mapped = false;
+    void* p = nullptr;
+    void* dev = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes, size_t keep = 0) {
+        if (cap >= bytes) return hipSuccess;
+        if (!keep) release();
+        const size_t want = std::max(bytes + bytes / 8, min_cap);
+        void* nb = nullptr;
+        hipError_t e = hipHostMalloc(&nb, want, mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        if (p) std::memcpy(nb, p, std::min(keep, cap));
+        release();
+        p = nb;
+        cap = want;
+        return mapped ? hipHostGetDevicePointer(&dev, p, 0) : hipSuccess;
+    }
+    void release() {
+        if (p) hipHostFree(p);
+        p = dev = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+enum BufId {
+    B_CAMS0, B_CAMS1, B_PTS0, B_PTS1, B_K0, B_K1, B_PRIOR,
+    B_PO_CAM, B_PO_AC, B_PO_UV, B_PO_DEP, B_PO_AP, B_PO_PT,
+    B_CO_PT, B_CO_UV, B_CO_DEP, B_RAW_CAM, B_RAW_PT, B_RAW_UV, B_RAW_DEP, B_PLAN,
+    B_CAMDATA, B_SEGINTR, B_LIN, B_SCALE, B_CNP, B_PDATA, B_S, B_RHS, B_DELTA, B_PART, B_SCAL, B_FLAG,
+    B_BCR, B_CAMDATA_LOC, B_ENV_LOC, B_RED, B_PREP, B_CAMPART, B_STATE, B_LOG, B_CAMS_INIT, B_PTS_INIT, B_K_INIT,
+    B_DBG0, B_DBG1, B_DBG2, B_DBG3, B_DET_TBUF, B_PO_REC, B_CO_REC,
+    B_RAW_ADM, B_DP_SCRATCH, B_DP_PO_DEST, B_DP_CO_DEST, B_DP_CAM_AC, B_DP_PT_IDX, B_DP_OVF, B_DP_SUM, B_TAIL_Y,
+    // ba_covariance (allocated on its first call): the two dense work matrices, the points' W_o scratch, the
+    // request's index lists + the status word, and the outputs
+    B_COV_A, B_COV_Z, B_COV_W, B_COV_IDX, B_COV_OUT,
+    // the blocked multi-workgroup Cholesky (BA_LS_BLOCKED): packed envelope blocks, diagonal inverses, padded rhs
+    // and the block lists
+    B_DENSE_A, B_DENSE_Z, B_DENSE_B, B_DENSE_IDX,
+    B_COUNT
+};
+
+struct ba_context {
+    ba_options opts;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t cov_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ba_covariance's own phase events (first call)
+    unsigned* hprog = nullptr;  // host-mapped LM progress word (LmParams::progress)
+    unsigned* dprog = nullptr;  // its device address
+    PinnedBuf hres;             // staging of the solved cameras + intrinsics (async device-to-host copies)
+    DevBuf buf[B_COUNT];
+    std::string err;
+    // host-side structure of the last prepared problem (ba_plan.h; plan.po_orig: point-major admissible obs ->
+    // original obs index)
+    miba::Plan plan;
+    std::vector<int> pt_idx, ac_cam;
+    miba::DensePlan dplan;       // BA_LS_BLOCKED: the envelope at 64-block granularity, kept with the plan
+    std::vector<int> dplan_idx;  // its device index buffer's host image (outlives the upload)
+    PinnedBuf stage{1 << 20};    // staging of ba_prepare's uploads: [raw observations | plan index arrays]
+    PinnedBuf pstage{1 << 16};   // staging of the parameter uploads (cameras | points | intrinsics | prior)
+    hipStream_t copy_stream = nullptr;  // the device plan's pixel DMA, beside the plan passes on `stream`
+    hipEvent_t ev_idx = nullptr, ev_uv = nullptr;  // indices / depths DMA'd; pixels DMA'd
+    bool uv_pending = false;  // the pixel DMA of the last prepare has not been waited for on `stream`
+    PinnedBuf rsum{256, true};  // the device plan's summary (ba_plan.h), mapped: the last pass writes it
+    std::vector<std::pair<size_t, size_t>> plan_parts;  // (offset, ints) of each array in B_PLAN (PlanPart order)
+    // plan cache (ba_options.rebuild_plan = 0): the structure key of the last full prepare; while plan_ok the
+    // staging buffer's raw region holds that window's observations (the reuse check compares against it) and
+    // `raw` the device gather inputs (B_RAW_* + the plan's orderings in B_PLAN)
+    struct PlanKey {
+        int nc = -1, np = -1, no = -1, fixed_cam = 0, det = 0, obs32 = 0;
+        unsigned long long env = 0;  // Settings::key
+        bool operator==(const PlanKey& o) const {
+            return nc == o.nc && np == o.np && no == o.no && fixed_cam == o.fixed_cam && det == o.det &&
+                   env == o.env;
+        }
+    } key;
+    bool plan_ok = false;
+    miba::Settings st;  // the MIBA_* settings of the prepare under way (read at its start; the key's env part)
+    miba::PrepRaw raw{};
+    ba_prepare_info pinfo{};
+    miba::DevProblem P{};
+    miba::DevWork W{};
+    miba::BaConsts C{};
+    int nblk_pt = 0;
+    bool prepared = false;
+    int n_tiles = 0, n_ovf_obs = 0, n_tiled_pts = 0;
+    int n_adm_all = 0;  // admissible observations over all landmark shards
+    int sw_full = 0;    // DevWork::sw as the last full prepare chose it (a timeout re-run clears W.sw)
+    int tail_full = 0;  // DevWork::tail likewise
+    int bsfin_full = 0;  // DevWork::bsfin likewise
+    bool tail_possible = false;  // the window's LM loop can take the band tail launch (set before bcr_setup)
+    int prep_nc = -1, prep_np = -1, prep_no = -1;
+    int last_iter = -1;        // iterations of the last solve (ba_iteration_log rows - 1)
+    int dbg_step_base = -1;    // ba_debug_step's slot of x while the device still holds what that step left behind
+    // shard_min_obs: a window below the threshold is gathered onto every rank and solved there alone; the
+    // communicator is parked meanwhile (restored by the next prepare), the rank's points are the slice
+    // [gather_off, gather_off + its n_points) of the gathered window
+    miba::Comm comm_parked;
+    int gather_off = 0;
+    int dev_np = 0;  // points on the device (the gathered window's when gathered)
+    struct Gathered {
+        std::vector<double> cams, pts, uv, dep;
+        std::vector<int> oc, op;
+        double intr[4], prior[4];
+    } gw;
+    bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
+    unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
+    int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout
+    // per-kernel profiling
+    miba::Prof prof;
+    bool prof_events = false;
+    int k_launches[miba::K_COUNT] = {0};
+    double k_ms[miba::K_COUNT] = {0};
+    double k_bytes[miba::K_COUNT] = {0};
+    double k_flops[miba::K_COUNT] = {0};
+    miba::Prof* pf() { return opts.profile_kernels ? &prof : nullptr; }
+};
+
+#define HIPCHECK(ctx, x)                                                                  \
+    do {                                                                                  \
+        hipError_t e_ = (x);                                                              \
+        if (e_ != hipSuccess) {                                                           \
+            (ctx)->err = std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x; \
+            return BA_E_DEVICE;                                                           \
+        }                                                                                 \
+    } while (0)
+
+// ---- ba_prepare.cpp
+// Uploads the window and builds (or reuses) its plan and device structure; the device work is left in flight.
+int prepare(ba_context* ctx, const ba_problem* p);
+// k_bcr_split's hand-off state as a prepare leaves it (also after 2^28 launches on one prepared window)
+int bcr_init_handoffs(ba_context* ctx);
+
+// ---- ba_solver.cpp: the enqueue code of an LM solve on the prepared window (ba_solve_prepared, ba_debug_step)
+void flush_prof(ba_context* ctx);
+int apply_spin_limit(ba_context* ctx);
+miba::LmState fresh_state(const ba_options& o, double radius);
+miba::LmParams lm_params(const ba_context* ctx);
+int enqueue_reset(ba_context* ctx, const miba::LmState& st0, int n_cams);
+int enqueue_iteration_zero(ba_context* ctx);
+int enqueue_iteration(ba_context* ctx, const miba::LmParams& prm);
+int bcr_timeout_retry(ba_context* ctx, miba::LmState& S);

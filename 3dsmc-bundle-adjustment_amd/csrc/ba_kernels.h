@@ -165,6 +165,37 @@ static constexpr unsigned long long BCR_Y_EMPTY = 0xFFF7A5A5FFF7A5A5ull;
 // [XL | XR | x] row stride (136 columns; padding to 144 for conflict-free operand rows measured no gain)
 static constexpr int BCR_XW = 136;
 static constexpr size_t BCR_BLOCK_DOUBLES = (size_t)5 * 64 * 64 + 64 * BCR_XW + 4 * 64 * 8 + 32 + 64;
+// The workspace of nblk blocks: the per-block members, F2, bk and the flags.
+inline size_t bcr_bytes(int nblk) {
+    return sizeof(double) * ((BCR_BLOCK_DOUBLES + 64 * 64) * nblk + 16) + sizeof(unsigned) * (16 + 6 * nblk);
+}
+// Lays the workspace out from `base` and returns its end (the caller checks it against bcr_bytes). The order is
+// part of the hand-off code, which fills neighbours in one call:
+//   Cf | X         the published panels, emptied together (bcr_init_handoffs)
+//   UL | UR | F    k_bcr_split's pull slots, reset together (bcr_reset_pull_slots)
+//   rL | rR        likewise
+//   Racc | Y       the y rows by epoch parity, emptied together (bcr_init_handoffs)
+inline const char* bcr_layout(BcrWork& Bw, double* base, int nblk) {
+    const size_t b64 = (size_t)64 * 64 * nblk, b8 = (size_t)64 * 8 * nblk;
+    double* q = base;
+    auto take = [&q](size_t n) { double* r = q; q += n; return r; };
+    Bw.Cf = take(b64);
+    Bw.X = take((size_t)64 * BCR_XW * nblk);
+    Bw.UL = take(b64);
+    Bw.UR = take(b64);
+    Bw.F = take(b64);
+    Bw.Dacc = take(b64);
+    Bw.rL = take(b8);
+    Bw.rR = take(b8);
+    Bw.Racc = take(b8);
+    Bw.Y = take(b8);
+    Bw.Bp = take((size_t)32 * nblk);
+    Bw.rd = take((size_t)64 * nblk);
+    Bw.F2 = take(b64);
+    Bw.bk = take(16);
+    Bw.flags = reinterpret_cast<unsigned*>(q);  // zeroed with the workspace (bcr_setup)
+    return reinterpret_cast<const char*>(Bw.flags + 16 + 6 * (size_t)nblk);
+}
 
 // Device-resident Levenberg-Marquardt state (Ceres 2.0 TrustRegionMinimizer +
 // LevenbergMarquardtStrategy bookkeeping, owned by k_lm_decide).
@@ -507,11 +538,12 @@ hipError_t launch_bcr(const DevProblem& P, const BaConsts& c, DevWork& W, BcrWor
 // 2 when the 2 * nblk workgroups of k_bcr_split can all be resident on the current device, else 1
 // when the nblk workgroups of k_bcr_persist can, else 0
 int bcr_persist_ok(int nblk);
-int bcr_xmap_ok(int nblk, int persist);
-int bcr_dense1_ok(int nblk, int kb);
-// cameras per block of the one-workgroup band solve for this window (0: not eligible; MIBA_BCR_BAND)
+// (the settings as arguments: Settings::bcr_xmap; bcr_set and bcr_dense1; bcr_set and bcr_band)
+int bcr_xmap_ok(int nblk, int persist, bool want);
+int bcr_dense1_ok(int nblk, int kb, bool bcr_set, bool want);
+// cameras per block of the one-workgroup band solve for this window (0: not eligible; mode: MIBA_BCR_BAND)
 // (one_block: also windows of one 64-dof block, where the band solve runs with its tail launch)
-int bcr_band_ok(int nac, int cam_band, int kb, bool one_block);
+int bcr_band_ok(int nac, int cam_band, int kb, bool one_block, bool bcr_set, int mode);
 hipError_t launch_bcr_band(const DevProblem& P, const BaConsts& c, DevWork& W, int bc, hipStream_t s, Prof* pf);
 // the band solve + back-substitution + final decision in one launch (W.tail): nb_pt / nb_upd / nb_bs as k_final's
 hipError_t launch_band_tail(const DevProblem& P, const BaConsts& c, const LmParams& prm, DevWork& W, int bc, int nb_pt,

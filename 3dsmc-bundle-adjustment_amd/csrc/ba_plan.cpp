@@ -219,12 +219,12 @@ void build_active_cameras(int nc, const std::vector<int>& cam_seen, int fixed_ca
 int host_threads() { return pool().size(); }
 void host_parallel(int n, const std::function<void(int)>& fn) { pool().run(n, fn); }
 
-// MIBA_PLAN_TIMES=1: per-phase wall times of the plan on stderr (diagnostic)
+// Plan::times (MIBA_PLAN_TIMES): per-phase wall times of the plan on stderr (diagnostic)
 struct PhaseTimer {
     bool on;
     double t;
     const char* stage;
-    explicit PhaseTimer(const char* s) : on(std::getenv("MIBA_PLAN_TIMES") != nullptr), t(now()), stage(s) {}
+    PhaseTimer(const char* s, bool on_) : on(on_), t(now()), stage(s) {}
     static double now() {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
     }
@@ -239,7 +239,7 @@ struct PhaseTimer {
 // ---------------------------------------------------------------- stage 1
 void plan_count(const PlanInput& in, Plan& pl) {
     const int nc = in.nc, np = in.np, no = in.no;
-    PhaseTimer tm("count");
+    PhaseTimer tm("count", pl.times);
     pl.err.clear();
     pl.cam_cnt.assign(nc, 0);
     pl.pt_cnt.assign(np, 0);
@@ -288,7 +288,7 @@ void plan_count(const PlanInput& in, Plan& pl) {
 void plan_order(const PlanInput& in, const std::vector<int>& cam_seen, const PlanParams& pp, Plan& pl) {
     const int nc = in.nc, np = in.np, no = in.no;
     const int n_adm = pl.n_adm;
-    PhaseTimer tm("order");
+    PhaseTimer tm("order", pl.times);
     pl.dev = false;
     build_active_cameras(nc, cam_seen, in.fixed_cam, pl);
     const int nac = pl.nac;
@@ -456,7 +456,7 @@ void plan_order(const PlanInput& in, const std::vector<int>& cam_seen, const Pla
 
 // ---------------------------------------------------------------- stage 2 from the device plan
 void plan_from_device(const int* sum, int nc, int np, int fixed_cam, const PlanParams& pp, Plan& pl) {
-    PhaseTimer tm("device");
+    PhaseTimer tm("device", pl.times);
     pl.dev = true;
     pl.cam_cnt.assign(sum + DP_HDR, sum + DP_HDR + nc);
     pl.pt_cnt.clear(); pl.adm.clear(); pl.pmin.clear(); pl.pmax.clear(); pl.task_cam.clear();

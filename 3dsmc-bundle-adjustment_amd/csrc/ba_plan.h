@@ -42,6 +42,7 @@ struct PlanParams {
 };
 
 struct Plan {
+    bool times = false;              // diagnostic (MIBA_PLAN_TIMES): per-phase wall times of the stages on stderr
     // ---- stage 1 (plan_count): validation, admissibility, counts
     std::string err;                 // non-empty: the problem is malformed
     std::vector<int> cam_cnt, pt_cnt;

@@ -224,7 +224,7 @@ typedef struct ba_prepare_info {
     int32_t bsfin;           /* 1: the point back-substitution and the LM decision run in one launch (larger
                                 unsharded windows, k_backsub_final; opt-in, MIBA_BSFIN=1) — version 2 */
 } ba_prepare_info;
-/* the smallest struct_size ba_last_prepare accepts: the fields through total_ms (the round-3 layout) */
+/* the smallest struct_size ba_last_prepare accepts: the v2 layout through total_ms */
 #define BA_PREPARE_INFO_MIN_SIZE ((int32_t)(offsetof(ba_prepare_info, total_ms) + sizeof(double)))
 #define BA_PREPARE_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 /* Writes min(info->struct_size, sizeof(ba_prepare_info)) bytes; BA_E_INVALID below BA_PREPARE_INFO_MIN_SIZE. */

@@ -4,11 +4,14 @@ The reference re-optimises the same window on every processed frame until the ne
 (main.cpp:163-168, SURVEY §3.1), and windowOptimize rebuilds its ceres::Problem each time
 (OptimizationUtils.cpp:218). libmiba keeps the host plan and the device structure of the last window and, when
 the next window has the same structure (sizes, gauge, obs_cam, obs_pt, admissibility mask), uploads only the
-parameters and the observation values that changed (ba_solver.cpp prepare_reuse).
+parameters and the observation values that changed (ba_prepare.cpp prepare_reuse).
 
 Checked here: a reused plan gives bitwise the same deterministic solve as a fresh context; changed pixel / depth
 values on the same structure are re-gathered; every structural change (one obs_pt, one admissibility flip, the
-gauge, a value that is no longer an exact f32 on an obs32 plan, the deterministic option) rebuilds."""
+gauge, a value that is no longer an exact f32 on an obs32 plan, the deterministic option) rebuilds, and so does a
+changed MIBA_* layout setting (MIBA_BSFIN, which the key once missed)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -185,3 +188,32 @@ def test_changed_cost_options_on_a_reused_plan(change):
     # and the change did matter (the old constants would have given another solve)
     base = _fresh(p)
     assert not np.array_equal(base[2], fresh[2]), "the option change did not change the solve"
+
+
+def test_bsfin_setting_is_part_of_the_plan_key():
+    """MIBA_BSFIN decides DevWork::bsfin in the prepare, so it is part of the plan key: setting or unsetting it
+    between two solves of one window rebuilds instead of silently keeping the last prepare's choice. (Before the
+    settings table, which keys every prepare-time variable it parses, the second solve reused the plan with
+    bsfin = 0.)"""
+    p = _prob("c2")
+    old = os.environ.pop("MIBA_BSFIN", None)
+    try:
+        with _solver(max_num_iterations=3) as s:
+            s.solve(p.copy())
+            i1 = s.last_prepare()
+            os.environ["MIBA_BSFIN"] = "1"
+            s.solve(p.copy())
+            i2 = s.last_prepare()
+            del os.environ["MIBA_BSFIN"]
+            s.solve(p.copy())
+            i3 = s.last_prepare()
+            s.solve(p.copy())
+            i4 = s.last_prepare()
+    finally:
+        os.environ.pop("MIBA_BSFIN", None)
+        if old is not None:
+            os.environ["MIBA_BSFIN"] = old
+    assert i1["plan_reused"] == 0 and i1["bsfin"] == 0, i1
+    assert i2["plan_reused"] == 0 and i2["bsfin"] == 1, i2
+    assert i3["plan_reused"] == 0 and i3["bsfin"] == 0, i3
+    assert i4["plan_reused"] == 1 and i4["bsfin"] == 0, i4
