@@ -22,15 +22,19 @@ struct BaConsts {
 };
 
 // Eigen toRotationMatrix of q = (w=p[3], x=p[0], y=p[1], z=p[2])  (OptimizationUtils.cpp:36-41)
+// Every linearising kernel must round an observation's residual the same way: the Huber corrector of a small
+// residual amplifies the rounding of u - uo by |u| / |u - uo|, and the camera side (U, C) and the point side
+// (W, V) of one observation nearly cancel in S when the point hangs on that observation. So quat_R and
+// obs_project spell their fused multiply-adds out and leave the compiler none to choose by context.
 __device__ __forceinline__ void quat_R(const double* __restrict__ p, double R[9]) {
+#pragma clang fp contract(off)
     const double x = p[0], y = p[1], z = p[2], w = p[3];
     const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
     const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+    const double txx = tx * x, tyy = ty * y, tzz = tz * z;
+    R[0] = 1 - (tyy + tzz);              R[1] = __builtin_fma(ty, x, -twz);  R[2] = __builtin_fma(tz, x, twy);
+    R[3] = __builtin_fma(ty, x, twz);    R[4] = 1 - (txx + tzz);             R[5] = __builtin_fma(tz, y, -twx);
+    R[6] = __builtin_fma(tz, x, -twy);   R[7] = __builtin_fma(tz, y, twx);   R[8] = 1 - (txx + tyy);
 }
 
 // 1/x: v_rcp_f64 + two Newton steps (within an ulp or two of the IEEE quotient; five dependent
@@ -41,6 +45,31 @@ __device__ __forceinline__ double rcp_f64(double x) {
     y = __builtin_fma(y, e, y);
     e = __builtin_fma(-x, y, 1.0);
     return __builtin_fma(y, e, y);
+}
+
+// The rotation R, the point in the camera frame (x, y, z), 1 / z and the pixel (u, v), in one fixed sequence of
+// operations.
+__device__ __forceinline__ void obs_project(const double* __restrict__ pose, const double* __restrict__ X,
+                                            const double* __restrict__ K, double R[9], double& x, double& y,
+                                            double& z, double& iz, double& u, double& v) {
+#pragma clang fp contract(off)
+    quat_R(pose, R);
+    const double d0 = X[0] - pose[4], d1 = X[1] - pose[5], d2 = X[2] - pose[6];
+    x = __builtin_fma(R[6], d2, __builtin_fma(R[3], d1, R[0] * d0));
+    y = __builtin_fma(R[7], d2, __builtin_fma(R[4], d1, R[1] * d0));
+    z = __builtin_fma(R[8], d2, __builtin_fma(R[5], d1, R[2] * d0));
+    iz = rcp_f64(z);
+    u = __builtin_fma(K[2], z, K[0] * x) * iz;
+    v = __builtin_fma(K[3], z, K[1] * y) * iz;
+}
+// The weighted residuals and the squared norm of the pixel pair (the Huber argument), likewise.
+__device__ __forceinline__ void obs_residual(const BaConsts& c, double u, double v, double z, double uo, double vo,
+                                             double depth, double& r0, double& r1, double& r2, double& s_uv) {
+#pragma clang fp contract(off)
+    r0 = c.sw_r * (u - uo);
+    r1 = c.sw_r * (v - vo);
+    r2 = c.sw_d * (depth - z);
+    s_uv = __builtin_fma(r1, r1, r0 * r0);
 }
 
 // Huber rho(s) and sqrt(rho'(s))  (Ceres HuberLoss::Evaluate; Corrector)
@@ -65,18 +94,11 @@ struct ObsEval {
 __device__ __forceinline__ void eval_obs(const BaConsts& c, const double* __restrict__ pose,
                                          const double* __restrict__ X, const double* __restrict__ K,
                                          double uo, double vo, double depth, ObsEval& o) {
-    double R[9];
-    quat_R(pose, R);
-    const double d0 = X[0] - pose[4], d1 = X[1] - pose[5], d2 = X[2] - pose[6];
-    const double x = R[0] * d0 + R[3] * d1 + R[6] * d2;
-    const double y = R[1] * d0 + R[4] * d1 + R[7] * d2;
-    const double z = R[2] * d0 + R[5] * d1 + R[8] * d2;
-    const double iz = rcp_f64(z);
-    const double u = (K[0] * x + K[2] * z) * iz;
-    const double v = (K[1] * y + K[3] * z) * iz;
-    const double r0 = c.sw_r * (u - uo), r1 = c.sw_r * (v - vo), r2 = c.sw_d * (depth - z);
+    double R[9], x, y, z, iz, u, v, r0, r1, r2, s_uv;
+    obs_project(pose, X, K, R, x, y, z, iz, u, v);
+    obs_residual(c, u, v, z, uo, vo, depth, r0, r1, r2, s_uv);
     double rr, gr, rd, gd;
-    huber(r0 * r0 + r1 * r1, c.a_r, c.b_r, rr, gr);
+    huber(s_uv, c.a_r, c.b_r, rr, gr);
     huber(r2 * r2, c.a_d, c.b_d, rd, gd);
     o.cost = 0.5 * rr + 0.5 * rd;
     o.f[0] = gr * r0; o.f[1] = gr * r1; o.f[2] = gd * r2;
@@ -89,19 +111,12 @@ __device__ __forceinline__ void lin_obs(const BaConsts& c, const double* __restr
                                         const double* __restrict__ X, const double* __restrict__ K,
                                         double uo, double vo, double depth, ObsEval& o, double jc[18],
                                         double jp[9], double jk[8]) {
-    double R[9];
-    quat_R(pose, R);
-    const double d0 = X[0] - pose[4], d1 = X[1] - pose[5], d2 = X[2] - pose[6];
-    const double x = R[0] * d0 + R[3] * d1 + R[6] * d2;
-    const double y = R[1] * d0 + R[4] * d1 + R[7] * d2;
-    const double z = R[2] * d0 + R[5] * d1 + R[8] * d2;
-    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];
-    const double iz = rcp_f64(z);
-    const double u = (fx * x + cx * z) * iz;
-    const double v = (fy * y + cy * z) * iz;
-    const double r0 = c.sw_r * (u - uo), r1 = c.sw_r * (v - vo), r2 = c.sw_d * (depth - z);
+    double R[9], x, y, z, iz, u, v, r0, r1, r2, s_uv;
+    obs_project(pose, X, K, R, x, y, z, iz, u, v);
+    obs_residual(c, u, v, z, uo, vo, depth, r0, r1, r2, s_uv);
+    const double fx = K[0], fy = K[1];
     double rr, gr, rd, gd;
-    huber(r0 * r0 + r1 * r1, c.a_r, c.b_r, rr, gr);
+    huber(s_uv, c.a_r, c.b_r, rr, gr);
     huber(r2 * r2, c.a_d, c.b_d, rd, gd);
     o.cost = 0.5 * rr + 0.5 * rd;
     o.f[0] = gr * r0; o.f[1] = gr * r1; o.f[2] = gd * r2;

@@ -16,7 +16,8 @@ without the gauge camera's columns and without cameras / points that have no adm
                  no normal equations. Dense: windows up to about 25 cameras.
 * ``schur_step`` the points eliminated one by one in extended precision (3x3 inverse from f64, Newton-corrected),
                  the reduced system solved by f64 Cholesky + extended-precision refinement, back-substitution.
-                 Also returns cond_2 of the scaled, damped reduced matrix.
+                 Also returns cond_2 of the scaled, damped reduced matrix. ``schur_reduce`` is its elimination alone:
+                 the reduced system in extended precision (refschur.schur_system rounds it to f64).
 
 Both return ``Step(ac_cam, delta_cam, delta_intr, delta_pts, model_cost_change, cond)``: the active cameras in
 increasing order, the parameter-space step of each (nac, 6), of the intrinsics (4,) and of every point in the caller's
@@ -177,8 +178,9 @@ def _inv3(V):
     return X
 
 
-def schur_step(prob, opts=None, radius: float = 0.0) -> Step:
-    L = _Lin(prob, opts, radius)
+def schur_reduce(L):
+    """The scaled, damped reduced system of ``L`` in extended precision — active cameras in increasing order, six
+    rows each, then the four intrinsics: (S, rhs, per active point (columns, [W_p; K_p], V_p^-1, g_p))."""
     nac, nr = L.nac, 6 * L.nac + 4
     kb = 6 * nac
     S = np.zeros((nr, nr), LD)
@@ -220,6 +222,13 @@ def schur_step(prob, opts=None, radius: float = 0.0) -> Step:
         S[np.ix_(cols, cols)] -= T @ E.T
         rhs[cols] += T @ gp
         keep.append((cols, E, Vi, gp))
+    return S, rhs, keep
+
+
+def schur_step(prob, opts=None, radius: float = 0.0) -> Step:
+    L = _Lin(prob, opts, radius)
+    kb = 6 * L.nac
+    S, rhs, keep = schur_reduce(L)
     S64 = S.astype(np.float64)
     S64 = (S64 + S64.T) / 2
     C = np.linalg.cholesky(S64)

@@ -66,6 +66,8 @@ Measured (MI355X; err = the largest of the three groups; gpu = the largest over 
   bcr21_messy      10000   1.33e+06  2.4e-09   2.8e-12   2.8e-12    1.2e-16   1
   nb37_b2_messy    10000   1.08e+06  1.9e-09   1.4e-11   3.0e-11    2.3e-16   1
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -81,10 +83,20 @@ BCR_MODES = {"launch": 0, "persist": 1, "split": 2, "split3": 3}
 def run_step(monkeypatch, name, radius=1e4, env=None, opts=None, comm=False, tag=""):
     """lm_step of window ``name`` under ``env`` / ``opts``, checked against the reference; returns (step, prepare
     info)."""
+    return run_prepared(monkeypatch, name, refstep.reference(name, radius), radius, env, opts, comm, tag)
+
+
+def run_prepared(monkeypatch, name, prepared, radius=1e4, env=None, opts=None, comm=False, tag=""):
+    """run_step on a prepared (window, schur_step, oracle.lm_step, the oracle's decision) — the tuple of
+    refstep.reference; ``name`` labels the printed line. Without ``monkeypatch`` (a child process) ``env`` goes
+    into os.environ."""
     from miba.solver import Solver
     for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    p, ref, orc, accepted = refstep.reference(name, radius)
+        if monkeypatch is None:
+            os.environ[k] = v
+        else:
+            monkeypatch.setenv(k, v)
+    p, ref, orc, accepted = prepared
     q = p.copy()
     kw = dict(NO_TOL)
     kw.update(opts or {})
