@@ -89,6 +89,9 @@ enum BufId {
     // the blocked multi-workgroup Cholesky (BA_LS_BLOCKED): packed envelope blocks, diagonal inverses, padded rhs
     // and the block lists
     B_DENSE_A, B_DENSE_Z, B_DENSE_B, B_DENSE_IDX,
+    // ba_residuals (allocated on its first call): the per-observation values in point-major slot order and in the
+    // caller's order (errors | cost | flags each), the block statistics with their partials and the totals
+    B_RES_PO, B_RES_OBS, B_RES_STAT,
     B_COUNT
 };
 
@@ -98,6 +101,7 @@ struct ba_context {
     hipStream_t stream = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t cov_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ba_covariance's own phase events (first call)
+    hipEvent_t res_ev[2] = {nullptr, nullptr};  // ba_residuals' events around its kernels (first call)
     unsigned* hprog = nullptr;  // host-mapped LM progress word (LmParams::progress)
     unsigned* dprog = nullptr;  // its device address
     PinnedBuf hres;             // staging of the solved cameras + intrinsics (async device-to-host copies)

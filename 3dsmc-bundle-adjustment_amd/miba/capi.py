@@ -223,6 +223,66 @@ COV_INTR = -1  # BA_COV_INTR
 COV_OK, COV_RANK_DEFICIENT = 0, 1
 
 
+class BaResRequest(C.Structure):
+    """Mirror of ``ba_res_request`` (ba_residuals). ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("max_reproj_px", C.c_double),
+        ("max_depth_abs", C.c_double),
+        ("max_depth_rel", C.c_double),
+        ("obs_err", _dp),
+        ("obs_cost", _dp),
+        ("obs_flags", _ip),
+        ("obs_depth_culled", _dp),
+        ("cam_stats", _dp),
+        ("point_stats", _dp),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaResInfo(C.Structure):
+    """Mirror of ``ba_res_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_admissible", C.c_int32),
+        ("n_outliers", C.c_int32),
+        ("n_behind", C.c_int32),
+        ("n_reproj", C.c_int32),
+        ("n_depth", C.c_int32),
+        ("n_huber_repr", C.c_int32),
+        ("n_huber_unpr", C.c_int32),
+        ("cost", C.c_double),
+        ("prior_cost", C.c_double),
+        ("rms_reproj_px", C.c_double),
+        ("max_reproj_px", C.c_double),
+        ("rms_depth", C.c_double),
+        ("max_depth", C.c_double),
+        ("time_eval_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
+# bits of obs_flags (BA_RES_*)
+RES_INADMISSIBLE, RES_BEHIND, RES_REPROJ, RES_DEPTH, RES_HUBER_REPR, RES_HUBER_UNPR = 1, 2, 4, 8, 16, 32
+RES_OUTLIER = RES_BEHIND | RES_REPROJ | RES_DEPTH
+RES_ERR_N, RES_STAT_N = 4, 6
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .capi import COV_INTR, LOG_FIELDS, BaCovInfo, BaCovRequest, BaKernelStat, BaOptions, BaPrepareInfo, BaSummary, ProblemArrays
+from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaKernelStat,
+                   BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
 def default_options(**overrides) -> BaOptions:
@@ -307,3 +308,57 @@ class Solver:
             out["full"] = fm
         out.update(info.as_dict())
         return out
+
+    def residuals(self, prob: ProblemArrays, max_reproj_px: float = 0.0, max_depth_abs: float = 0.0,
+                  max_depth_rel: float = 0.0, per_obs: bool = True, per_block: bool = True) -> dict:
+        """The residual report of the window at ``prob``'s parameters (ba_residuals; ``prob`` is not modified).
+
+        ``per_obs``: ``err`` (n_obs, 4) = du, dv [px], depth - z, z; ``cost`` (n_obs,), the observation's share of
+        the solver's cost; ``flags`` (n_obs,) int32, the capi.RES_* bits; ``depth_culled`` (n_obs,), ``obs_depth``
+        with the RES_OUTLIER observations set to 0. ``per_block``: ``cam_stats`` (n_cams, 6) and ``point_stats``
+        (n_points, 6): admissible, outliers, sum du^2 + dv^2, max sqrt(du^2 + dv^2), sum (depth - z)^2, sum cost.
+        All in the caller's order; inadmissible observations are NaN with flag RES_INADMISSIBLE. The dict also
+        carries the fields of ``ba_res_info`` (counts, prior_cost, rms / max errors, time_*_ms), its ``cost`` under
+        the name ``total_cost``. Thresholds <= 0 switch a test off."""
+        i32p = C.POINTER(C.c_int32)
+        req, info = BaResRequest(), BaResInfo()
+        req.max_reproj_px, req.max_depth_abs, req.max_depth_rel = float(max_reproj_px), float(max_depth_abs), float(max_depth_rel)
+        out = {}
+        n = prob.n_obs
+        if per_obs:
+            out.update(err=np.zeros((n, RES_ERR_N)), cost=np.zeros(n), flags=np.zeros(n, dtype=np.int32),
+                       depth_culled=np.zeros(n))
+            req.obs_err, req.obs_cost, req.obs_depth_culled = _dptr(out["err"]), _dptr(out["cost"]), _dptr(out["depth_culled"])
+            req.obs_flags = out["flags"].ctypes.data_as(i32p)
+        if per_block:
+            out.update(cam_stats=np.zeros((prob.n_cams, RES_STAT_N)), point_stats=np.zeros((prob.n_points, RES_STAT_N)))
+            req.cam_stats, req.point_stats = _dptr(out["cam_stats"]), _dptr(out["point_stats"])
+        ps = prob.struct()
+        self._check(self._L.ba_residuals(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_residuals")
+        d = info.as_dict()
+        d["total_cost"] = d.pop("cost")  # (``cost`` is the per-observation array)
+        out.update(d)
+        return out
+
+    def solve_culled(self, prob: ProblemArrays, max_reproj_px: float, max_depth_abs: float = 0.0,
+                     max_depth_rel: float = 0.0, rounds: int = 2) -> dict:
+        """Solve, drop the outliers, solve again (the loop of ORB-SLAM's local BA, on the host): after each solve
+        the report at the solution (``residuals`` with the thresholds given); the loop ends when it flags no
+        observation that is still in, or after ``rounds`` solves. Flagged observations get depth 0 in a working
+        copy of the depths (the solver skips them and N, the normaliser of the weights, counts the rest); the next
+        solve starts from the parameters already reached. The caller's observation arrays are never written;
+        ``prob``'s cameras, points and intrinsics hold the last solution. Returns ``summaries`` (one per solve),
+        ``report`` (the last one) and ``culled`` (n_obs,) bool."""
+        work = ProblemArrays(prob.cams, prob.points, prob.intr, prob.intr_prior, prob.obs_cam, prob.obs_pt, prob.obs_uv,
+                             prob.obs_depth.copy(), int(prob.fixed_cam))
+        culled = np.zeros(prob.n_obs, dtype=bool)
+        summaries, report = [], None
+        for _ in range(max(int(rounds), 1)):
+            summaries.append(self.solve(work))
+            report = self.residuals(work, max_reproj_px, max_depth_abs, max_depth_rel, per_block=False)
+            new = (report["flags"] & RES_OUTLIER) != 0
+            if not new.any():
+                break
+            culled |= new
+            work.obs_depth[new] = 0.0
+        return dict(summaries=summaries, report=report, culled=culled)

@@ -49,7 +49,9 @@ extern "C" {
  *      version with BA_E_INVALID.
  *   2, additive  ba_covariance with ba_cov_request / ba_cov_info (both sized structs); nothing else changed.
  *   2, additive  BA_LS_BLOCKED, a fourth value of ba_summary.linear_solver (wide co-visibility windows); no struct
- *                changed. */
+ *                changed.
+ *   2, additive  ba_residuals with ba_res_request / ba_res_info (both sized structs) and the BA_RES_* flags; nothing
+ *                else changed. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -321,6 +323,66 @@ typedef struct ba_cov_info {
 #define BA_COV_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 #define BA_COV_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 int32_t ba_covariance(ba_context* ctx, const ba_problem* prob, const ba_cov_request* req, ba_cov_info* info);
+
+/* ---- residual report (the counterpart of ceres::Problem::Evaluate) ----
+ * What every observation of the window is off by at prob's parameters, in physical units, which keyframes and
+ * landmarks carry the error, and which observations are outliers against the caller's thresholds.
+ * Per observation, in the caller's order: obs_err = du, dv [px] (projected minus measured pixel), depth - z and z (the
+ * point's depth in the camera frame): the raw differences, without the 1/N weights and without the Huber corrector;
+ * obs_cost = 0.5 rho_repr + 0.5 rho_unpr, the observation's share of the cost the LM loop minimises (weights and
+ * Huber loss applied), the value the solver's candidate evaluation computes; obs_flags, the BA_RES_* bits. An
+ * observation the solver skips (depth <= 1e-15) has NaN errors and cost and the flag BA_RES_INADMISSIBLE alone.
+ * BA_RES_REPROJ compares sqrt(du^2 + dv^2), formed with IEEE multiply, add and square root, the value the maxima
+ * report; BA_RES_DEPTH uses max(max_depth_abs, 0) + max(max_depth_rel, 0) * depth. Both tests are plain comparisons:
+ * one with a NaN operand does not flag.
+ * obs_depth_culled is prob->obs_depth with the BA_RES_OUTLIER observations set to 0: passed as obs_depth of the next
+ * solve it makes the solver skip them (and N, the weights' normaliser, counts the rest).
+ * Per block (cam_stats: every camera of the window, the gauge camera included; point_stats: every point), six values:
+ *   [0] admissible observations   [1] of those, with a BA_RES_OUTLIER bit   [2] sum du^2 + dv^2
+ *   [3] max sqrt(du^2 + dv^2)     [4] sum (depth - z)^2                       [5] sum obs_cost
+ * [2], [3], [4] run over the block's projected observations (admissible and not BA_RES_BEHIND: a pixel that is not
+ * finite stays out of the sums), [0], [1], [5] over all admissible ones. A block without an admissible observation is
+ * all zeros. ba_res_info carries the same over the whole window: rms = sqrt(sum / projected count), 0 without a
+ * projected observation; cost = sum obs_cost + prior_cost, the cost ba_debug_linearize reports.
+ * Every sum has a fixed order (no floating-point atomics): the report is bitwise reproducible from call to call,
+ * with ba_options.deterministic 0 or 1 and with the host or the device plan; the camera sums (and the totals formed
+ * from them) follow the camera sub-segments (MIBA_SUBSEG), everything else does not depend on any setting.
+ * Behaves like ba_covariance: prepares the window (the plan cache applies) and evaluates at prob's parameters; prob
+ * is not modified, and a following ba_solve / ba_solve_prepared behaves as if the call had not happened. A window
+ * without an admissible observation returns 0 with zero counts and cost = prior_cost. Contexts with landmark shards:
+ * BA_E_INVALID. */
+/* bits of obs_flags */
+#define BA_RES_INADMISSIBLE 0x01 /* depth <= 1e-15: the solver skips it; its err / cost are NaN */
+#define BA_RES_BEHIND       0x02 /* z <= 0 in the camera frame, or the projected pixel is not finite */
+#define BA_RES_REPROJ       0x04 /* hypot(du, dv) > max_reproj_px */
+#define BA_RES_DEPTH        0x08 /* |depth - z| > max_depth_abs + max_depth_rel * depth */
+#define BA_RES_HUBER_REPR   0x10 /* reprojection block in Huber's linear zone (weighted s > a^2) */
+#define BA_RES_HUBER_UNPR   0x20 /* depth-prior block in Huber's linear zone */
+#define BA_RES_OUTLIER      (BA_RES_BEHIND | BA_RES_REPROJ | BA_RES_DEPTH)
+#define BA_RES_ERR_N  4  /* du, dv [px] = projected - measured; depth - z; z (camera-frame depth) */
+#define BA_RES_STAT_N 6  /* see above */
+typedef struct ba_res_request {
+    int32_t struct_size, reserved0;       /* BA_RES_REQUEST_INIT */
+    double max_reproj_px;                 /* <= 0: no reprojection test */
+    double max_depth_abs, max_depth_rel;  /* both <= 0: no depth test */
+    double*  obs_err;          /* optional [n_obs * 4], original observation order */
+    double*  obs_cost;         /* optional [n_obs]: 0.5 rho_repr + 0.5 rho_unpr, this observation's share of the cost */
+    int32_t* obs_flags;        /* optional [n_obs] */
+    double*  obs_depth_culled; /* optional [n_obs]: prob->obs_depth with the BA_RES_OUTLIER observations set to 0 */
+    double*  cam_stats;        /* optional [n_cams * 6], every camera of the window, the gauge camera included */
+    double*  point_stats;      /* optional [n_points * 6] */
+} ba_res_request;
+typedef struct ba_res_info {
+    int32_t struct_size, n_admissible, n_outliers, n_behind, n_reproj, n_depth, n_huber_repr, n_huber_unpr;
+    double cost, prior_cost;              /* cost = what ba_debug_linearize reports; prior_cost the IntrinsicsPrior share */
+    double rms_reproj_px, max_reproj_px, rms_depth, max_depth;
+    double time_eval_ms, time_total_ms;   /* the kernels (HIP events); the whole call, prepare and copies included */
+} ba_res_info;
+#define BA_RES_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_res_request))
+#define BA_RES_INFO_MIN_SIZE ((int32_t)sizeof(ba_res_info))
+#define BA_RES_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_RES_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_residuals(ba_context* ctx, const ba_problem* prob, const ba_res_request* req, ba_res_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the
