@@ -92,6 +92,9 @@ enum BufId {
     // ba_residuals (allocated on its first call): the per-observation values in point-major slot order and in the
     // caller's order (errors | cost | flags each), the block statistics with their partials and the totals
     B_RES_PO, B_RES_OBS, B_RES_STAT,
+    // ba_covisibility (allocated on its first call): its own copy of the observation indices and depths, the
+    // camera x point bit matrix, the weights, and the cameras' positions with the points' spans and the two counts
+    B_COVIS_OBS, B_COVIS_BITS, B_COVIS_W, B_COVIS_SPAN,
     B_COUNT
 };
 
@@ -102,6 +105,7 @@ struct ba_context {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t cov_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ba_covariance's own phase events (first call)
     hipEvent_t res_ev[2] = {nullptr, nullptr};  // ba_residuals' events around its kernels (first call)
+    hipEvent_t covis_ev[2] = {nullptr, nullptr};  // ba_covisibility's events around its count kernels (first call)
     unsigned* hprog = nullptr;  // host-mapped LM progress word (LmParams::progress)
     unsigned* dprog = nullptr;  // its device address
     PinnedBuf hres;             // staging of the solved cameras + intrinsics (async device-to-host copies)
@@ -160,6 +164,12 @@ struct ba_context {
         std::vector<int> oc, op;
         double intr[4], prior[4];
     } gw;
+    // ba_solve_ordered's shadow problem: the cameras as placed, the observations' camera indices remapped, and the
+    // order it computes itself (order == NULL)
+    struct Ordered {
+        std::vector<double> cams;
+        std::vector<int32_t> obs_cam, inv, order;
+    } ordered;
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
     int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout

@@ -283,6 +283,50 @@ RES_OUTLIER = RES_BEHIND | RES_REPROJ | RES_DEPTH
 RES_ERR_N, RES_STAT_N = 4, 6
 
 
+class BaCovisRequest(C.Structure):
+    """Mirror of ``ba_covis_request`` (ba_covisibility). ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("weights", _ip),
+        ("order", _ip),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaCovisInfo(C.Structure):
+    """Mirror of ``ba_covis_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_active", C.c_int32),
+        ("n_edges", C.c_int32),
+        ("n_components", C.c_int32),
+        ("band_before", C.c_int32),
+        ("band_after", C.c_int32),
+        ("wide_before", C.c_int32),
+        ("wide_after", C.c_int32),
+        ("order_changed", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("time_count_ms", C.c_double),
+        ("time_order_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved0")}
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

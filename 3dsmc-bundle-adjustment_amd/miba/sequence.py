@@ -85,9 +85,10 @@ def make_tum_sequence(n_keyframes: int = 36, n_landmarks: int = 1500, seed: int 
 
 
 def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_frequency: int = 10,
-                 window_size: int = 10):
+                 window_size: int = 10, order=None):
     """main.cpp:150-195 with one keyframe per frame. Returns (trajectory_text, summaries, intr_opt);
-    ``keyframes`` / ``landmarks`` are updated in place."""
+    ``keyframes`` / ``landmarks`` are updated in place. ``order`` (opt-in, default off) goes to
+    window.window_optimize: ``"auto"`` solves every window in its co-visibility order."""
     intr_opt = np.array(intr_init, dtype=np.float64)
     summaries = []
     pending = list(keyframes)
@@ -100,7 +101,8 @@ def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_fre
         run, a, b, fin = window.window_schedule(frame_frequency, window_size, len(keyframes), not tracked,
                                                 finished, tracked)
         if run:
-            summaries.append((a, b, window.window_optimize(a, b, keyframes, landmarks, intr_init, intr_opt, solve)))
+            summaries.append((a, b, window.window_optimize(a, b, keyframes, landmarks, intr_init, intr_opt, solve,
+                                                           order=order)))
         finished = finished or fin
         if not tracked:  # after the sequence ends the schedule can fire at most once
             break

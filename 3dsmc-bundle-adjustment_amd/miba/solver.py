@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaKernelStat,
+from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaCovisInfo,
+                   BaCovisRequest, BaKernelStat,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -70,11 +71,47 @@ class Solver:
         """ba_last_error() of this context: the error of the last failed call, or a note of the last solve."""
         return (self._L.ba_last_error(self._h) or b"").decode()
 
-    def solve(self, prob: ProblemArrays) -> dict:
+    def solve(self, prob: ProblemArrays, order=None) -> dict:
+        """ba_solve; with ``order`` ba_solve_ordered: ``"auto"`` computes the camera order from the window's
+        co-visibility first (ba_covisibility), an array is the order to use (order[k] = the camera placed k-th, as
+        ``covisibility`` returns it). The cameras come back in the caller's numbering either way; the summary, the
+        iteration log and ``last_prepare`` describe the ordered window."""
         s = BaSummary()
         ps = prob.struct()
-        self._check(self._L.ba_solve(self._h, C.byref(ps), C.byref(s)), "ba_solve")
+        if order is None:
+            self._check(self._L.ba_solve(self._h, C.byref(ps), C.byref(s)), "ba_solve")
+            return s.as_dict()
+        optr = None
+        if not (isinstance(order, str) and order == "auto"):
+            o = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+            if len(o) != prob.n_cams:
+                raise ValueError("order must have one entry per camera")
+            optr = o.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._L.ba_solve_ordered(self._h, C.byref(ps), optr, C.byref(s)), "ba_solve_ordered")
         return s.as_dict()
+
+    def covisibility(self, prob: ProblemArrays, weights: bool = True, order: bool = True) -> dict:
+        """The keyframe co-visibility graph of the window and the camera order that narrows its band
+        (ba_covisibility; ``prob`` is not modified, the context's plan and LM state are not touched).
+
+        ``weights`` (n_cams, n_cams) int32: distinct points two cameras both see through admissible observations, a
+        camera's own count on the diagonal. ``order`` (n_cams,) int32: order[k] = the camera placed k-th (the
+        identity unless the order narrows the band without widening any point past the Schur tile window). The dict
+        also carries the fields of ``ba_covis_info``: n_active, n_edges, n_components, band_before / band_after,
+        wide_before / wide_after, order_changed, time_*_ms."""
+        i32p = C.POINTER(C.c_int32)
+        req, info = BaCovisRequest(), BaCovisInfo()
+        out = {}
+        if weights:
+            out["weights"] = np.zeros((prob.n_cams, prob.n_cams), dtype=np.int32)
+            req.weights = out["weights"].ctypes.data_as(i32p)
+        if order:
+            out["order"] = np.zeros(prob.n_cams, dtype=np.int32)
+            req.order = out["order"].ctypes.data_as(i32p)
+        ps = prob.struct()
+        self._check(self._L.ba_covisibility(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_covisibility")
+        out.update(info.as_dict())
+        return out
 
     @staticmethod
     def comm_unique_id() -> bytes:

@@ -64,8 +64,10 @@ class KeyFrame:
 
 
 def window_optimize(kf_i: int, kf_f: int, keyframes: list, landmarks: dict, intr_init, intr_opt: np.ndarray,
-                    solve) -> dict:
-    """windowOptimize (:215-313). ``landmarks``: LandmarkId -> (3,) point; ``intr_opt`` updated in place."""
+                    solve, order=None) -> dict:
+    """windowOptimize (:215-313). ``landmarks``: LandmarkId -> (3,) point; ``intr_opt`` updated in place.
+    ``order`` (opt-in, default off): passed on as ``solve(prob, order=order)``, for a ``miba.solver.Solver().solve``
+    -- ``"auto"`` solves the window in its co-visibility order (ba_solve_ordered)."""
     T0 = np.array(keyframes[kf_i].T_w_c, dtype=np.float64)
     T0inv = se3_inv(T0)
     cams = []
@@ -98,7 +100,7 @@ def window_optimize(kf_i: int, kf_f: int, keyframes: list, landmarks: dict, intr
                              np.array(obs_cam, dtype=np.int32), np.array(obs_pt, dtype=np.int32),
                              np.array(uv, dtype=np.float64).reshape(-1, 2), np.array(depth, dtype=np.float64),
                              fixed_cam=0)
-        summary = solve(prob)
+        summary = solve(prob) if order is None else solve(prob, order=order)
         intr_opt[:] = prob.intr
         for k, lid in enumerate(ids):
             landmarks[lid] = prob.points[k].copy()

@@ -51,7 +51,9 @@ extern "C" {
  *   2, additive  BA_LS_BLOCKED, a fourth value of ba_summary.linear_solver (wide co-visibility windows); no struct
  *                changed.
  *   2, additive  ba_residuals with ba_res_request / ba_res_info (both sized structs) and the BA_RES_* flags; nothing
- *                else changed. */
+ *                else changed.
+ *   2, additive  ba_covisibility with ba_covis_request / ba_covis_info (both sized structs) and ba_solve_ordered;
+ *                nothing else changed. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -383,6 +385,60 @@ typedef struct ba_res_info {
 #define BA_RES_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 #define BA_RES_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 int32_t ba_residuals(ba_context* ctx, const ba_problem* prob, const ba_res_request* req, ba_res_info* info);
+
+/* ---- keyframe co-visibility and the camera ordering ----
+ * The fast paths of the solver need co-visible cameras to be numbered close together, in active-camera index space:
+ * the Schur tiles take a point whose cameras lie inside 12 consecutive active cameras, the block cyclic reduction a
+ * camera_band below 10. A window numbered in time order that sees the scene more than once (global BA, a loop
+ * closure, a hand-held sweep) falls off both although its co-visibility graph is as sparse as a sliding window's.
+ * ba_covisibility reports that graph and an order of the cameras that narrows the band; ba_solve_ordered solves the
+ * window in such an order.
+ * weights: W[a][b] = the distinct points cameras a and b both see through admissible observations (depth > 1e-15),
+ * W[a][a] = the distinct points a sees; an observation repeated for the same camera and point counts once; the gauge
+ * camera is included. The input of a co-visibility-driven window selection.
+ * order: order[k] = the camera of the window placed k-th. Reverse Cuthill-McKee over the active cameras (those with
+ * an admissible observation, the gauge camera apart; an edge where W > 0): per connected component, from the
+ * unvisited camera of lowest (degree, index) breadth-first, a camera's unvisited neighbours by (degree, index), the
+ * component's list reversed; the components in the order they were started, then the gauge camera and the cameras
+ * without an admissible observation in index order. The order is returned only if it narrows the band
+ * (band_after < band_before) and sends no more points to the Schur stage's overflow path (wide_after <= wide_before);
+ * otherwise the identity, order_changed = 0 and band_after / wide_after repeat the before values: a sliding window
+ * keeps its numbering.
+ * Stand-alone: validates the window as ba_prepare does, works on copies of obs_cam / obs_pt / obs_depth in device
+ * buffers of its own and touches neither the context's plan nor its LM state: a ba_solve_prepared after it is bitwise
+ * the solve without it. Integer arithmetic only: the report is bitwise reproducible. A window without an admissible
+ * observation returns 0 with zero weights and the identity order. Contexts with landmark shards: BA_E_INVALID. */
+typedef struct ba_covis_request {
+    int32_t struct_size, reserved0;  /* BA_COVIS_REQUEST_INIT */
+    int32_t* weights;                /* optional [n_cams * n_cams], row-major, symmetric */
+    int32_t* order;                  /* optional [n_cams] */
+} ba_covis_request;
+typedef struct ba_covis_info {
+    int32_t struct_size;
+    int32_t n_active;                  /* cameras with an admissible observation, the gauge camera apart */
+    int32_t n_edges;                   /* co-visible pairs of active cameras */
+    int32_t n_components;              /* connected components of the active cameras' graph */
+    int32_t band_before, band_after;   /* what ba_summary.camera_band is as given / would be in `order` */
+    int32_t wide_before, wide_after;   /* points whose active cameras span more than 12 positions (overflow points) */
+    int32_t order_changed;             /* 1: `order` is not the identity */
+    int32_t reserved0;
+    double time_count_ms;              /* the bit-matrix and weight kernels (HIP events) */
+    double time_order_ms;              /* the ordering on the host and the span kernels */
+    double time_total_ms;              /* the whole call, uploads and copies included */
+} ba_covis_info;
+#define BA_COVIS_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_covis_request))
+#define BA_COVIS_INFO_MIN_SIZE ((int32_t)sizeof(ba_covis_info))
+#define BA_COVIS_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_COVIS_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_covisibility(ba_context* ctx, const ba_problem* prob, const ba_covis_request* req, ba_covis_info* info);
+
+/* ba_solve on the window with its cameras placed in `order` (a permutation of 0 .. n_cams-1, as ba_covisibility
+ * returns it; NULL: computed by ba_covisibility first). The context keeps a shadow problem (the cameras permuted,
+ * obs_cam and fixed_cam remapped; points, intrinsics and the other observation arrays are the caller's), runs
+ * ba_solve on it and copies the cameras back to the caller's positions; points and intrinsics are updated in place
+ * as usual. summary, ba_iteration_log, ba_last_prepare and the plan cache describe the ordered window: a repeat of
+ * the same structure with the same order reuses the plan. Contexts with landmark shards: BA_E_INVALID. */
+int32_t ba_solve_ordered(ba_context* ctx, ba_problem* prob, const int32_t* order, ba_summary* summary);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the

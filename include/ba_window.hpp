@@ -105,8 +105,19 @@ struct WindowProblem {
     }
 };
 
+// The solver of a libmiba context for windowOptimize below. ordered = false (default): ba_solve. ordered = true
+// (opt-in): ba_solve_ordered with the order computed from the window's co-visibility, for windows whose keyframes see
+// the scene more than once (global BA with window_size = -1, loop closures); a sliding window keeps its numbering
+// either way, at the price of the co-visibility pass.
+template <class Context>
+auto window_solver(Context* ctx, bool ordered = false) {
+    return [ctx, ordered](ba_problem* p, ba_summary* s) -> int32_t {
+        return ordered ? ba_solve_ordered(ctx, p, nullptr, s) : ba_solve(ctx, p, s);
+    };
+}
+
 // windowOptimize with an injectable solver: solve(ba_problem*, ba_summary*) -> int32_t
-// (e.g. [&](ba_problem* p, ba_summary* s) { return ba_solve(ctx, p, s); }).
+// (e.g. window_solver(ctx), or [&](ba_problem* p, ba_summary* s) { return ba_solve(ctx, p, s); }).
 // Returns true like the reference (:312); the solver status is returned through *status.
 template <class KeyFrames, class Map3D, class Vec4In, class Vec4Out, class SolveFn>
 bool windowOptimize(int kf_i, int kf_f, KeyFrames& keyframes, Map3D& map, const Vec4In& intrinsics_initial,
