@@ -95,6 +95,10 @@ enum BufId {
     // ba_covisibility (allocated on its first call): its own copy of the observation indices and depths, the
     // camera x point bit matrix, the weights, and the cameras' positions with the points' spans and the two counts
     B_COVIS_OBS, B_COVIS_BITS, B_COVIS_W, B_COVIS_SPAN,
+    // the constant cameras' mask for the device plan (ba_set_constant_cameras)
+    B_DP_CONST,
+    // ba_local_window (allocated on its first call): the integer scratch of the selection and its outputs
+    B_LOCAL_WORK, B_LOCAL_OUT,
     B_COUNT
 };
 
@@ -130,11 +134,15 @@ struct ba_context {
     struct PlanKey {
         int nc = -1, np = -1, no = -1, fixed_cam = 0, det = 0, obs32 = 0;
         unsigned long long env = 0;  // Settings::key
+        std::vector<uint8_t> cmask;  // the constant cameras in force (empty: none)
         bool operator==(const PlanKey& o) const {
             return nc == o.nc && np == o.np && no == o.no && fixed_cam == o.fixed_cam && det == o.det &&
-                   env == o.env;
+                   env == o.env && cmask == o.cmask;
         }
     } key;
+    // ba_set_constant_cameras: [n_cams] 0 / 1 as given (empty: none set); cmask_any: it has a member
+    std::vector<uint8_t> cmask;
+    bool cmask_any = false;
     bool plan_ok = false;
     miba::Settings st;  // the MIBA_* settings of the prepare under way (read at its start; the key's env part)
     miba::PrepRaw raw{};
@@ -170,6 +178,13 @@ struct ba_context {
         std::vector<double> cams;
         std::vector<int32_t> obs_cam, inv, order;
     } ordered;
+    // ba_solve_local's shadow problem (the sub-window of the last call) and the selection's host outputs
+    struct Local {
+        std::vector<double> cams, pts, uv, dep;
+        std::vector<int32_t> w, cam_index, pt_index, obs_index, obs_cam, obs_pt;
+        std::vector<uint8_t> cam_constant, is_local;  // per sub-window camera: constant; a member of L
+    } local;
+    hipEvent_t local_ev[2] = {nullptr, nullptr};  // ba_local_window's events around its kernels (first call)
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
     int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout

@@ -92,10 +92,16 @@ extern "C" int32_t ba_covisibility(ba_context* ctx, const ba_problem* p, const b
     // the candidate order on the host, then what it does to the points' spans on the device
     const double t_order = now_ms();
     CamOrder co;
-    covis_order(W, p->n_cams, p->fixed_cam, co);
+    // the context's constant cameras count as the gauge camera does (a mask set for another n_cams: BA_E_INVALID, as
+    // a prepare of this window would say)
+    if (ctx->cmask_any && ctx->cmask.size() != nc)
+        return invalid("the window has " + std::to_string(p->n_cams) + " cameras, the constant-camera mask was set for " +
+                       std::to_string(ctx->cmask.size()));
+    const uint8_t* cam_const = ctx->cmask_any ? ctx->cmask.data() : nullptr;
+    covis_order(W, p->n_cams, p->fixed_cam, cam_const, co);
     std::vector<int32_t> pos(2 * nc), given;
     for (int i = 0; i < p->n_cams; ++i)
-        if (W[nc * i + i] > 0 && i != p->fixed_cam) given.push_back(i);
+        if (W[nc * i + i] > 0 && i != p->fixed_cam && !(cam_const && cam_const[i])) given.push_back(i);
     positions(given.data(), co.n_active, p->n_cams, pos.data());
     positions(co.order.data(), co.n_active, p->n_cams, pos.data() + nc);
     int32_t wide[2] = {0, 0};
@@ -168,7 +174,12 @@ extern "C" int32_t ba_solve_ordered(ba_context* ctx, ba_problem* p, const int32_
     shadow.cams = sh.cams.data();
     shadow.obs_cam = sh.obs_cam.data();
     if (p->fixed_cam >= 0 && p->fixed_cam < nc) shadow.fixed_cam = sh.inv[p->fixed_cam];
+    // the shadow problem carries the constant cameras at their new positions; the caller's mask is back afterwards
+    const std::vector<uint8_t> given_mask = ctx->cmask;
+    if (ctx->cmask_any && ctx->cmask.size() == (size_t)nc)
+        for (int k = 0; k < nc; ++k) ctx->cmask[k] = given_mask[order[k]];
     const int32_t rc = ba_solve(ctx, &shadow, sum);
+    ctx->cmask = given_mask;
     if (rc != BA_OK) return rc;
     for (int k = 0; k < nc; ++k) std::memcpy(p->cams + (size_t)order[k] * 7, &sh.cams[(size_t)k * 7], 7 * sizeof(double));
     return BA_OK;

@@ -35,6 +35,8 @@ struct DPlanArgs {
     int* sum_host;  // device address of mapped host memory: the summary's live ranges are copied there last
     // scratch (device), dplan_scratch_ints() ints
     int* scratch;
+    // input (device), [nc] or nullptr: the constant cameras beside fixed_cam (PlanInput::cam_const)
+    const unsigned char* cam_const = nullptr;
 };
 size_t dplan_scratch_ints(int no, int np, int nc);
 // the window fits the device plan (bucket histograms in LDS, the packed camera range of the summary)

@@ -16,6 +16,7 @@
 // sync between them; admissibility comes in as one byte per observation (the host computes it while staging), so
 // the passes read neither depths nor pixels, whose DMA runs beside them on the copy stream.
 #include "ba_dplan.h"
+#include "ba_scan.h"
 
 #include <algorithm>
 #include <climits>
@@ -33,6 +34,7 @@ constexpr long long HIST_MAX = 1LL << 22;     // bucket histogram entries (range
 // every device pointer of the plan (kernel argument, by value)
 struct DP {
     const int* cam; const int* pt; const unsigned char* adm;
+    const unsigned char* cam_const;           // [nc] or nullptr: constant cameras beside fixed_cam
     int no, np, nc, fixed_cam, tile_win, chunk_obs;
     int ro, rp, nwo, nwp;                     // observations / points per range, ranges
     int* po_dest; int* co_dest; int* cam_ac; int* pt_idx; int* ovf_obs;
@@ -45,28 +47,7 @@ struct DP {
     int nsb;
 };
 
-// exclusive scan of one int per thread over the block (TPB threads); total = the block's sum
-__device__ inline int block_excl(int v, int* sh, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) sh[w] = x;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < TPB / 64; ++j) {
-        const int s = sh[j];
-        off += j < w ? s : 0;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return off + x - v;
-}
+static_assert(TPB == SCAN_TPB, "block_excl (ba_scan.h) scans one workgroup of TPB threads");
 
 // exclusive scan of one int per lane over the wave; total = the wave's sum
 __device__ inline int wave_excl(int v, int& total) {
@@ -166,14 +147,15 @@ __global__ __launch_bounds__(TPB) void k_dp_rowscan(int* H, int nw, int* T) {
     if (threadIdx.x == 0) T[blockIdx.x] = carry;
 }
 
-// cameras: counts (summary), camera-major segment starts, active cameras (observed, not the gauge), fc[a] = a
+// cameras: counts (summary), camera-major segment starts, active cameras (observed, neither the gauge nor in the
+// constant set), fc[a] = a
 __global__ __launch_bounds__(TPB) void k_dp_cams(DP d) {
     __shared__ int sh[TPB / 64];
     int cb = 0, ca = 0;
     for (int base = 0; base < d.nc; base += TPB) {
         const int c = base + threadIdx.x;
         const int cnt = c < d.nc ? d.Tc[c] : 0;
-        const int act = (c < d.nc && cnt > 0 && c != d.fixed_cam) ? 1 : 0;
+        const int act = (c < d.nc && cnt > 0 && c != d.fixed_cam && !(d.cam_const && d.cam_const[c])) ? 1 : 0;
         int tb, ta;
         const int eb = block_excl(cnt, sh, tb);
         const int ea = block_excl(act, sh, ta);
@@ -544,7 +526,7 @@ bool dplan_fits(int no, int np, int nc) {
 hipError_t dplan_enqueue(const DPlanArgs& a, hipStream_t s) {
     const Geo g(a.no, a.np, a.nc);
     DP d{};
-    d.cam = a.cam; d.pt = a.pt; d.adm = a.adm;
+    d.cam = a.cam; d.pt = a.pt; d.adm = a.adm; d.cam_const = a.cam_const;
     d.no = a.no; d.np = a.np; d.nc = a.nc; d.fixed_cam = a.fixed_cam; d.tile_win = a.tile_win;
     d.chunk_obs = a.chunk_obs;
     d.ro = g.ro; d.rp = g.rp; d.nwo = g.nwo; d.nwp = g.nwp; d.nsb = g.nsb;

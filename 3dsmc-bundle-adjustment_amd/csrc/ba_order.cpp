@@ -19,12 +19,16 @@ int covis_band(const int32_t* W, int n_cams, const int32_t* order, int n_active)
 }
 
 void covis_order(const int32_t* W, int n_cams, int fixed_cam, CamOrder& out) {
+    covis_order(W, n_cams, fixed_cam, nullptr, out);
+}
+
+void covis_order(const int32_t* W, int n_cams, int fixed_cam, const uint8_t* cam_const, CamOrder& out) {
     const int n = n_cams;
     out = CamOrder{};
     std::vector<char> act(n, 0);
     std::vector<int32_t> given;  // the active cameras as given
     for (int i = 0; i < n; ++i)
-        if (W[(size_t)i * n + i] > 0 && i != fixed_cam) { act[i] = 1; given.push_back(i); }
+        if (W[(size_t)i * n + i] > 0 && i != fixed_cam && !(cam_const && cam_const[i])) { act[i] = 1; given.push_back(i); }
     out.n_active = (int)given.size();
     std::vector<int> deg(n, 0);
     for (int i : given) {

@@ -21,6 +21,9 @@ struct CamOrder {
 // the order they were started; then the gauge camera and the cameras without an admissible observation, in index
 // order. Integer only, deterministic.
 void covis_order(const int32_t* W, int n_cams, int fixed_cam, CamOrder& out);
+// The same with a set of constant cameras (cam_const[n_cams], non-zero = constant; nullptr: none) treated as the gauge
+// camera is: not nodes, placed after the active cameras in index order.
+void covis_order(const int32_t* W, int n_cams, int fixed_cam, const uint8_t* cam_const, CamOrder& out);
 
 // max a - fc[a] over the first n_active entries of `order`, fc[a] = the lowest position of a camera co-visible with
 // the camera at position a.

@@ -205,12 +205,16 @@ void build_segments(int nc, const std::vector<int>& cstart, const PlanParams& pp
         }
 }
 
-// active cameras (Ceres removes unused blocks; the gauge block is constant, :299)
-void build_active_cameras(int nc, const std::vector<int>& cam_seen, int fixed_cam, Plan& pl) {
+// active cameras (Ceres removes unused blocks; the gauge block is constant, :299, and so is every camera of the
+// constant set)
+void build_active_cameras(int nc, const std::vector<int>& cam_seen, int fixed_cam, const uint8_t* cam_const, Plan& pl) {
     pl.cam_ac.assign(nc, -1);
     pl.ac_cam.clear();
     for (int i = 0; i < nc; ++i)
-        if (cam_seen[i] && i != fixed_cam) { pl.cam_ac[i] = (int)pl.ac_cam.size(); pl.ac_cam.push_back(i); }
+        if (cam_seen[i] && i != fixed_cam && !(cam_const && cam_const[i])) {
+            pl.cam_ac[i] = (int)pl.ac_cam.size();
+            pl.ac_cam.push_back(i);
+        }
     pl.nac = (int)pl.ac_cam.size();
 }
 
@@ -290,7 +294,7 @@ void plan_order(const PlanInput& in, const std::vector<int>& cam_seen, const Pla
     const int n_adm = pl.n_adm;
     PhaseTimer tm("order", pl.times);
     pl.dev = false;
-    build_active_cameras(nc, cam_seen, in.fixed_cam, pl);
+    build_active_cameras(nc, cam_seen, in.fixed_cam, in.cam_const, pl);
     const int nac = pl.nac;
     const int* cam_ac = pl.cam_ac.data();
     // CSR of admissible obs by original point index, each list ordered by (active camera, obs index): the order
@@ -455,7 +459,8 @@ void plan_order(const PlanInput& in, const std::vector<int>& cam_seen, const Pla
 }
 
 // ---------------------------------------------------------------- stage 2 from the device plan
-void plan_from_device(const int* sum, int nc, int np, int fixed_cam, const PlanParams& pp, Plan& pl) {
+void plan_from_device(const int* sum, int nc, int np, int fixed_cam, const PlanParams& pp, Plan& pl,
+                      const uint8_t* cam_const) {
     PhaseTimer tm("device", pl.times);
     pl.dev = true;
     pl.cam_cnt.assign(sum + DP_HDR, sum + DP_HDR + nc);
@@ -464,7 +469,7 @@ void plan_from_device(const int* sum, int nc, int np, int fixed_cam, const PlanP
     pl.ovf_obs.clear();
     std::vector<int> cam_seen(nc);
     for (int i = 0; i < nc; ++i) cam_seen[i] = pl.cam_cnt[i] > 0;
-    build_active_cameras(nc, cam_seen, fixed_cam, pl);
+    build_active_cameras(nc, cam_seen, fixed_cam, cam_const, pl);
     const int nac = pl.nac;
     const int* fc = sum + DP_HDR + nc;
     const int* ptp = fc + nc;

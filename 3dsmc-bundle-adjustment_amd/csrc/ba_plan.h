@@ -29,6 +29,9 @@ struct PlanInput {
     const int32_t* obs_pt = nullptr;
     const double* obs_depth = nullptr;
     const double* obs_uv = nullptr;  // nullptr: no obs32 check (Plan::obs32 stays false)
+    // [nc] or nullptr: non-zero = the camera's pose is a constant block beside fixed_cam (ba_set_constant_cameras):
+    // no active index, its observations stay in every list
+    const uint8_t* cam_const = nullptr;
 };
 
 struct PlanParams {
@@ -98,7 +101,8 @@ inline size_t dplan_sum_ints(int nc, int np) { return (size_t)DP_HDR + 2 * (size
 
 // the host plan's stage 2 from the device plan's summary (counts, fc, the point order's columns): active cameras,
 // pt_ptr, Schur tiles, back-substitution chunks, camera sub-segments. n_adm / obs32 / err are the caller's.
-void plan_from_device(const int* sum, int nc, int np, int fixed_cam, const PlanParams& pp, Plan& pl);
+void plan_from_device(const int* sum, int nc, int np, int fixed_cam, const PlanParams& pp, Plan& pl,
+                      const uint8_t* cam_const = nullptr);
 
 // stage 1: index validation + admissibility + per-camera / per-point admissible counts
 void plan_count(const PlanInput& in, Plan& pl);

@@ -154,6 +154,10 @@ int prepare(ba_context* ctx, const ba_problem* p) {
     }
     ctx->gather_off = 0;
     ctx->dev_np = p && p->n_points > 0 ? p->n_points : 0;
+    if (ctx->W.comm.on() && ctx->cmask_any) {  // before any collective: every rank's own verdict
+        ctx->err = "constant cameras (ba_set_constant_cameras) are not supported on contexts with landmark shards";
+        return BA_E_INVALID;
+    }
     if (ctx->W.comm.on())
         if (int rc = shard_replicas_agree(ctx, p)) return rc;
     if (ctx->W.comm.on() && ctx->opts.shard_min_obs > 0) {
@@ -537,6 +541,12 @@ static int run_dplan(ba_context* ctx, Win& w) {
     a.sum = ctx->buf[B_DP_SUM].as<int>();
     a.sum_host = static_cast<int*>(ctx->rsum.dev);
     a.scratch = ctx->buf[B_DP_SCRATCH].as<int>();
+    if (ctx->cmask_any) {  // prepare_core has checked its size against nc
+        HIPCHECK(ctx, ctx->buf[B_DP_CONST].ensure((size_t)nc));
+        HIPCHECK(ctx, hipMemcpyAsync(ctx->buf[B_DP_CONST].p, ctx->cmask.data(), (size_t)nc, hipMemcpyHostToDevice, s));
+        a.cam_const = ctx->buf[B_DP_CONST].as<unsigned char>();
+    }
+    const uint8_t* cam_const = ctx->cmask_any ? ctx->cmask.data() : nullptr;
     HIPCHECK(ctx, dplan_enqueue(a, s));
     mark("enqueue");
     // a helper thread waits for the passes and builds the host side of the plan (tiles, chunks, segments) from the
@@ -546,7 +556,7 @@ static int run_dplan(ba_context* ctx, Win& w) {
     auto build_host_side = [&]() {
         helper_err = hipStreamSynchronize(s);
         if (helper_err == hipSuccess && sm[DP_TOOLONG] == 0 && sm[DP_BAD] == INT_MAX) {
-            plan_from_device(sm, nc, np, p->fixed_cam, plan_params(sm[DP_NADM], ctx->st), ctx->plan);
+            plan_from_device(sm, nc, np, p->fixed_cam, plan_params(sm[DP_NADM], ctx->st), ctx->plan, cam_const);
             w.dplan_built = true;
         }
     };
@@ -1140,7 +1150,7 @@ static int order_and_envelope(ba_context* ctx, Win& w, const PlanInput& in) {
     }
     const PlanParams pp = plan_params(pl.n_adm, ctx->st);
     if (w.dplan) {
-        if (!w.dplan_built) plan_from_device(ctx->rsum.as<int>(), w.nc, w.np, in.fixed_cam, pp, pl);
+        if (!w.dplan_built) plan_from_device(ctx->rsum.as<int>(), w.nc, w.np, in.fixed_cam, pp, pl, in.cam_const);
     } else {
         plan_order(in, cam_seen, pp, pl);
     }
@@ -1162,6 +1172,14 @@ static int prepare_core(ba_context* ctx, const ba_problem* p, bool force_det) {
     ctx->plan.times = ctx->st.plan_times;
     std::string local_err = validate(p);
     int bad = local_err.empty() ? 0 : 1;
+    // the constant cameras (ba_set_constant_cameras) belong to one n_cams (landmark shards: refused in prepare())
+    if (!bad && !ctx->cmask.empty()) {
+        if ((size_t)p->n_cams != ctx->cmask.size()) {
+            ctx->err = "the window has " + std::to_string(p->n_cams) + " cameras, the constant-camera mask was set for " +
+                       std::to_string(ctx->cmask.size()) + " (ba_set_constant_cameras)";
+            return BA_E_INVALID;
+        }
+    }
     if (!bad) { w.p = p; w.nc = p->n_cams; w.np = p->n_points; w.no = p->n_obs; }
     // plan cache: a window with the last full prepare's structure reuses its plan (unsharded contexts)
     ba_context::PlanKey key{};
@@ -1169,6 +1187,7 @@ static int prepare_core(ba_context* ctx, const ba_problem* p, bool force_det) {
     key.fixed_cam = bad ? -1 : p->fixed_cam;
     key.det = w.want_det ? 1 : 0;
     key.env = ctx->st.key;
+    if (!bad && ctx->cmask_any) key.cmask = ctx->cmask;
     if (!bad && !w.shard && !force_det && !ctx->opts.rebuild_plan && ctx->plan_ok && key == ctx->key) {
         const int r = prepare_reuse(ctx, p, w.tp0);
         if (r != 0) {
@@ -1188,6 +1207,7 @@ static int prepare_core(ba_context* ctx, const ba_problem* p, bool force_det) {
     PlanInput in;
     in.nc = w.nc; in.np = w.np; in.no = w.no;
     in.fixed_cam = bad ? -1 : p->fixed_cam;
+    if (!bad && ctx->cmask_any) in.cam_const = ctx->cmask.data();
     if (!bad) { in.obs_cam = p->obs_cam; in.obs_pt = p->obs_pt; in.obs_depth = p->obs_depth; }
     // obs32 records when every admissible pixel / depth is an f32 (the reference's are); MIBA_OBS32=0: f64 arrays
     if (!bad && ctx->st.obs32) in.obs_uv = p->obs_uv;

@@ -130,6 +130,8 @@ void ba_destroy(ba_context* ctx) {
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->covis_ev)
         if (e) hipEventDestroy(e);
+    for (auto& e : ctx->local_ev)
+        if (e) hipEventDestroy(e);
     if (ctx->prof_events)
         for (int i = 0; i < 2 * Prof::MAXP; ++i) hipEventDestroy(ctx->prof.ev[i]);
     if (ctx->hprog) hipHostFree(ctx->hprog);
@@ -208,6 +210,19 @@ int32_t ba_set_options(ba_context* ctx, const ba_options* opts) {
     }
     ctx->prof.on = ctx->opts.profile_kernels ? 1 : 0;
     ctx->prof.mask = (unsigned)ctx->opts.profile_mask;
+    return BA_OK;
+}
+
+int32_t ba_set_constant_cameras(ba_context* ctx, const uint8_t* is_constant, int32_t n_cams) {
+    if (!ctx) { g_err = "null context"; return BA_E_INVALID; }
+    if (n_cams < 0) { ctx->err = "ba_set_constant_cameras: negative n_cams"; return BA_E_INVALID; }
+    ctx->cmask.clear();
+    ctx->cmask_any = false;
+    if (is_constant)
+        for (int32_t i = 0; i < n_cams; ++i) {
+            ctx->cmask.push_back(is_constant[i] ? 1 : 0);
+            ctx->cmask_any = ctx->cmask_any || is_constant[i];
+        }
     return BA_OK;
 }
 
@@ -661,6 +676,9 @@ extern "C" int32_t ba_covariance(ba_context* ctx, const ba_problem* p, const ba_
     std::vector<int> cam_ac(std::max(p->n_cams, 1), COV_PAIR_NAN), idx(2 * (size_t)npairs + nreq);
     for (int t = 0; t < P.nac; ++t) cam_ac[ctx->ac_cam[t]] = t;
     if (p->fixed_cam >= 0 && p->fixed_cam < p->n_cams) cam_ac[p->fixed_cam] = COV_PAIR_ZERO;
+    if (ctx->cmask_any)  // a constant block like the gauge camera (prepare() has checked the mask's size)
+        for (int i = 0; i < p->n_cams; ++i)
+            if (ctx->cmask[i]) cam_ac[i] = COV_PAIR_ZERO;
     for (int k = 0; k < npairs; ++k) {
         idx[k] = req->pair_a[k] == BA_COV_INTR ? COV_PAIR_INTR : cam_ac[req->pair_a[k]];
         idx[npairs + k] = req->pair_b[k] == BA_COV_INTR ? COV_PAIR_INTR : cam_ac[req->pair_b[k]];

@@ -327,6 +327,57 @@ class BaCovisInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved0")}
 
 
+_u8p = C.POINTER(C.c_uint8)
+
+
+class BaLocalRequest(C.Structure):
+    """Mirror of ``ba_local_request`` (ba_local_window / ba_solve_local). ``struct_size`` is set to this mirror's size
+    on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("center", C.c_int32),
+        ("min_weight", C.c_int32),
+        ("max_local", C.c_int32),
+        ("w", _ip),
+        ("cam_index", _ip),
+        ("cam_constant", _u8p),
+        ("cam_local", _u8p),
+        ("pt_index", _ip),
+        ("obs_index", _ip),
+        ("sub_obs_cam", _ip),
+        ("sub_obs_pt", _ip),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaLocalInfo(C.Structure):
+    """Mirror of ``ba_local_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_local", C.c_int32),
+        ("n_fixed", C.c_int32),
+        ("n_points", C.c_int32),
+        ("n_obs", C.c_int32),
+        ("sub_fixed_cam", C.c_int32),
+        ("time_select_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

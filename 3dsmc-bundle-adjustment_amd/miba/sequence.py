@@ -85,10 +85,12 @@ def make_tum_sequence(n_keyframes: int = 36, n_landmarks: int = 1500, seed: int 
 
 
 def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_frequency: int = 10,
-                 window_size: int = 10, order=None):
+                 window_size: int = 10, order=None, solve_local=None, min_weight: int = 15, max_local: int = 0):
     """main.cpp:150-195 with one keyframe per frame. Returns (trajectory_text, summaries, intr_opt);
     ``keyframes`` / ``landmarks`` are updated in place. ``order`` (opt-in, default off) goes to
-    window.window_optimize: ``"auto"`` solves every window in its co-visibility order."""
+    window.window_optimize: ``"auto"`` solves every window in its co-visibility order. ``solve_local`` (opt-in,
+    default off; a ``Solver().solve_local``): whenever the schedule fires, window.local_optimize centred on the
+    newest keyframe of the window (``min_weight``, ``max_local``) in place of the last-k window."""
     intr_opt = np.array(intr_init, dtype=np.float64)
     summaries = []
     pending = list(keyframes)
@@ -100,7 +102,10 @@ def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_fre
             keyframes.append(pending.pop(0))
         run, a, b, fin = window.window_schedule(frame_frequency, window_size, len(keyframes), not tracked,
                                                 finished, tracked)
-        if run:
+        if run and solve_local is not None:
+            summaries.append((a, b, window.local_optimize(b, keyframes, landmarks, intr_init, intr_opt, solve_local,
+                                                          min_weight=min_weight, max_local=max_local)))
+        elif run:
             summaries.append((a, b, window.window_optimize(a, b, keyframes, landmarks, intr_init, intr_opt, solve,
                                                            order=order)))
         finished = finished or fin

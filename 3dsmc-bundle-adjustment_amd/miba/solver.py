@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaCovisInfo,
-                   BaCovisRequest, BaKernelStat,
+                   BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -44,6 +44,7 @@ class Solver:
         if not h:
             raise MibaError("ba_create failed: " + (self._L.ba_last_error(None) or b"").decode())
         self._h = h
+        self._cmask = None  # the constant cameras in force (set_constant_cameras), a bool array or None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -112,6 +113,65 @@ class Solver:
         self._check(self._L.ba_covisibility(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_covisibility")
         out.update(info.as_dict())
         return out
+
+    def set_constant_cameras(self, mask) -> None:
+        """ba_set_constant_cameras: ``mask`` (n_cams,) non-zero = the camera's pose is a constant parameter block in
+        every later prepare on this solver, in addition to the problem's ``fixed_cam``; ``None`` (or an empty mask)
+        clears the set. The mask is copied."""
+        if mask is None or len(mask) == 0:
+            self._check(self._L.ba_set_constant_cameras(self._h, None, 0), "ba_set_constant_cameras")
+            self._cmask = None
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        self._check(self._L.ba_set_constant_cameras(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), len(m)),
+                    "ba_set_constant_cameras")
+        self._cmask = m.astype(bool)
+
+    def _local_call(self, prob: ProblemArrays, center: int, min_weight: int, max_local: int, summary):
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        req, info = BaLocalRequest(), BaLocalInfo()
+        req.center, req.min_weight, req.max_local = int(center), int(min_weight), int(max_local)
+        nc, npt, no = max(prob.n_cams, 1), max(prob.n_points, 1), max(prob.n_obs, 1)
+        w = np.zeros(nc, dtype=np.int32)
+        cam_index = np.zeros(nc, dtype=np.int32)
+        cam_constant, cam_local = np.zeros(nc, dtype=np.uint8), np.zeros(nc, dtype=np.uint8)
+        pt_index = np.zeros(npt, dtype=np.int32)
+        obs_index, sub_cam, sub_pt = (np.zeros(no, dtype=np.int32) for _ in range(3))
+        req.w, req.cam_index, req.pt_index = (a.ctypes.data_as(i32p) for a in (w, cam_index, pt_index))
+        req.cam_constant, req.cam_local = cam_constant.ctypes.data_as(u8p), cam_local.ctypes.data_as(u8p)
+        req.obs_index, req.sub_obs_cam, req.sub_obs_pt = (a.ctypes.data_as(i32p) for a in (obs_index, sub_cam, sub_pt))
+        ps = prob.struct()
+        if summary is None:
+            self._check(self._L.ba_local_window(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_local_window")
+        else:
+            self._check(self._L.ba_solve_local(self._h, C.byref(ps), C.byref(req), C.byref(info), C.byref(summary)),
+                        "ba_solve_local")
+        n = info.n_local + info.n_fixed
+        out = dict(w=w[: prob.n_cams].copy(), cam_index=cam_index[:n].copy(), cam_constant=cam_constant[:n].astype(bool),
+                   cam_local=cam_local[:n].astype(bool), pt_index=pt_index[: info.n_points].copy(),
+                   obs_index=obs_index[: info.n_obs].copy(), sub_obs_cam=sub_cam[: info.n_obs].copy(),
+                   sub_obs_pt=sub_pt[: info.n_obs].copy())
+        out.update(info.as_dict())
+        return out
+
+    def local_window(self, prob: ProblemArrays, center: int, min_weight: int = 15, max_local: int = 0) -> dict:
+        """The co-visibility-selected window around camera ``center`` of the map ``prob`` (ba_local_window; ``prob`` is
+        not modified, the context's plan and LM state are not touched). ``w`` (n_cams,): points shared with the
+        centre; ``cam_index``: the sub-window's cameras (local and fixed ones, increasing), ``cam_local`` /
+        ``cam_constant`` flags per such camera; ``pt_index``; ``obs_index`` with the renumbered ``sub_obs_cam`` /
+        ``sub_obs_pt``; and the fields of ``ba_local_info`` (n_local, n_fixed, n_points, n_obs, sub_fixed_cam,
+        time_*_ms)."""
+        return self._local_call(prob, center, min_weight, max_local, None)
+
+    def solve_local(self, prob: ProblemArrays, center: int, min_weight: int = 15, max_local: int = 0) -> dict:
+        """ba_solve_local: select the window around ``center`` and solve it with its fixed cameras constant; the
+        local cameras, the local points and the intrinsics of ``prob`` are updated in place, everything else is
+        untouched. Returns the summary of the sub-window's solve with the selection under ``"window"``."""
+        s = BaSummary()
+        win = self._local_call(prob, center, min_weight, max_local, s)
+        d = s.as_dict()
+        d["window"] = win
+        return d
 
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -308,6 +368,8 @@ class Solver:
         has[np.asarray(prob.obs_cam)[adm]] = True
         if 0 <= prob.fixed_cam < prob.n_cams:
             has[prob.fixed_cam] = False
+        if self._cmask is not None and len(self._cmask) == prob.n_cams:
+            has[self._cmask] = False
         ac_cam = np.nonzero(has)[0].astype(np.int32)
         if pairs is None:
             pairs = [(int(c), int(c)) for c in ac_cam] + [(COV_INTR, COV_INTR)]

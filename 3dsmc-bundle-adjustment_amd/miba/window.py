@@ -115,6 +115,17 @@ def window_optimize(kf_i: int, kf_f: int, keyframes: list, landmarks: dict, intr
     return summary
 
 
+def local_optimize(kf_c: int, keyframes: list, landmarks: dict, intr_init, intr_opt: np.ndarray, solve_local,
+                   min_weight: int = 15, max_local: int = 0) -> dict:
+    """The opt-in local schedule: in place of the last-k window, the map so far (keyframes 0 .. kf_c, flattened as
+    window_optimize flattens a window, keyframe 0 the map's gauge) handed to ``solve_local`` -- a
+    ``miba.solver.Solver().solve_local`` -- centred on keyframe ``kf_c``: the keyframes co-visible with it are
+    optimised with the landmarks they see, every other keyframe that sees those landmarks is held constant
+    (ba_solve_local). The rest of the map is not touched."""
+    return window_optimize(0, kf_c, keyframes, landmarks, intr_init, intr_opt,
+                           lambda prob: solve_local(prob, kf_c, min_weight=min_weight, max_local=max_local))
+
+
 def window_schedule(frame_frequency: int, window_size: int, n_keyframes: int, tracking_finished: bool,
                     optimization_finished: bool, tracked_this_frame: bool):
     """(run, kf_i, kf_f, finishes) for main.cpp:163-183."""

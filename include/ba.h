@@ -53,7 +53,9 @@ extern "C" {
  *   2, additive  ba_residuals with ba_res_request / ba_res_info (both sized structs) and the BA_RES_* flags; nothing
  *                else changed.
  *   2, additive  ba_covisibility with ba_covis_request / ba_covis_info (both sized structs) and ba_solve_ordered;
- *                nothing else changed. */
+ *                nothing else changed.
+ *   2, additive  ba_set_constant_cameras (a set of constant poses beside fixed_cam), ba_local_window with
+ *                ba_local_request / ba_local_info (both sized structs) and ba_solve_local; nothing else changed. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -439,6 +441,80 @@ int32_t ba_covisibility(ba_context* ctx, const ba_problem* prob, const ba_covis_
  * as usual. summary, ba_iteration_log, ba_last_prepare and the plan cache describe the ordered window: a repeat of
  * the same structure with the same order reuses the plan. Contexts with landmark shards: BA_E_INVALID. */
 int32_t ba_solve_ordered(ba_context* ctx, ba_problem* prob, const int32_t* order, ba_summary* summary);
+
+/* ---- constant cameras and the local window (local bundle adjustment) ----
+ * is_constant[n_cams]: non-zero = the camera's pose is a constant parameter block in every later prepare on this
+ * context (ba_prepare, ba_solve, ba_solve_ordered, the debug hooks, ba_covariance, ba_residuals), in addition to
+ * prob->fixed_cam: ceres::Problem::SetParameterBlockConstant on several blocks. NULL or n_cams == 0 clears the set.
+ * The mask is copied. A constant camera's observations stay admissible: they count in N, contribute to their points'
+ * blocks and to the intrinsics and are part of the cost; its pose has no columns in the reduced system and comes back
+ * bitwise as given; num_active_cams, reduced_system_size and camera_band describe the remaining cameras; a
+ * ba_covariance pair that involves it is all zeros; ba_covisibility / ba_solve_ordered place it after the active
+ * cameras as they place the gauge camera. Every camera constant is legal: the window is solved on its points and the
+ * intrinsics. The mask is part of the plan-cache key (same mask: the plan is reused; changed mask: a new plan); the
+ * host plan and the device plan (MIBA_DEVICE_PLAN) are built from it alike. A prepare whose n_cams differs from the
+ * mask's returns BA_E_INVALID; so does one on a context with landmark shards while the set has a member. */
+int32_t ba_set_constant_cameras(ba_context* ctx, const uint8_t* is_constant, int32_t n_cams);
+
+/* ba_local_window selects, from a whole map given as a ba_problem, the window a local bundle adjustment around camera
+ * `center` optimises (the local BA of ORB-SLAM-style back-ends). All of it is integer:
+ *   w[a]  the distinct points cameras center and a both see through admissible observations (row `center` of
+ *         ba_covisibility's weights, one and-popcount row of the camera x point bit matrix; w[center] = its points);
+ *   L     the local cameras: center, plus every a with w[a] >= min_weight (<= 0: 1); if that exceeds max_local
+ *         (<= 0: no cap), center and the max_local - 1 others of largest (w[a], -a): larger weight first, lower index
+ *         on a tie;
+ *   P     the local points: every point with an admissible observation in a camera of L;
+ *   F     the fixed cameras: every camera outside L with an admissible observation of a point of P.
+ * The sub-window: cameras L u F in increasing original index (cam_index; the map's numbering is kept, a sliding window
+ * keeps its band), points P in increasing original index (pt_index), every admissible observation whose point is in
+ * P, in the caller's order (obs_index; a stable compaction, inadmissible observations dropped), with its camera and
+ * point renumbered (sub_obs_cam, sub_obs_pt). Constant in the sub-window (cam_constant): every camera of F, the map's
+ * fixed_cam if it is in L u F, and the cameras of the context's constant set when one is set for the map's n_cams. If
+ * that leaves nothing constant, the lowest camera of L is the sub-window's gauge (sub_fixed_cam, an index into
+ * cam_index) and cam_constant is all zeros; otherwise sub_fixed_cam = -1.
+ * Every output buffer is optional and sized by the caller for the worst case (n_cams, n_points, n_obs entries).
+ * Stand-alone like ba_covisibility: validates the map as ba_prepare does, works on device buffers of its own and
+ * touches neither the context's plan nor its LM state. The sort of at most n_cams weights runs on the host; bit rows,
+ * popcounts, the points' ranks and the observations' compaction (flags, exclusive scan, scatter) are kernels. A
+ * center without an admissible observation returns 0 with L = {center}, P, F and the observations empty and
+ * sub_fixed_cam = 0. center out of range, contexts with landmark shards: BA_E_INVALID. */
+typedef struct ba_local_request {
+    int32_t struct_size, center;     /* BA_LOCAL_REQUEST_INIT */
+    int32_t min_weight, max_local;
+    int32_t* w;                      /* optional [n_cams] */
+    int32_t* cam_index;              /* optional [n_local + n_fixed]: original indices of the sub-window's cameras */
+    uint8_t* cam_constant;           /* optional [n_local + n_fixed] */
+    uint8_t* cam_local;              /* optional [n_local + n_fixed]: 1 = the camera is in L */
+    int32_t* pt_index;               /* optional [info.n_points] */
+    int32_t* obs_index;              /* optional [info.n_obs]: original indices of the kept observations */
+    int32_t* sub_obs_cam;            /* optional [info.n_obs] */
+    int32_t* sub_obs_pt;             /* optional [info.n_obs] */
+} ba_local_request;
+typedef struct ba_local_info {
+    int32_t struct_size;
+    int32_t n_local, n_fixed;        /* |L|, |F| */
+    int32_t n_points, n_obs;         /* of the sub-window */
+    int32_t sub_fixed_cam;
+    double time_select_ms;           /* the kernels (HIP events) */
+    double time_total_ms;            /* the whole call, uploads, the host's sort and copies included */
+} ba_local_info;
+#define BA_LOCAL_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_local_request))
+#define BA_LOCAL_INFO_MIN_SIZE ((int32_t)sizeof(ba_local_info))
+#define BA_LOCAL_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_LOCAL_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_local_window(ba_context* ctx, const ba_problem* prob, const ba_local_request* req, ba_local_info* info);
+
+/* ba_local_window, then ba_solve on the sub-window under its constant set. The context keeps the sub-window as a
+ * shadow problem (cameras and points gathered, obs_uv / obs_depth gathered by obs_index; intrinsics and prior are the
+ * caller's), solves it and copies L's cameras and P's points back to their places in prob. The intrinsics are
+ * optimised against the prior as in every ba_solve (the reference's sliding windows do the same). Cameras outside L,
+ * points outside P and constant cameras stay bitwise untouched, and the context's own constant set is back in force
+ * afterwards. req's output buffers are filled as by ba_local_window. A sub-window without an observation: nothing is
+ * solved and nothing in prob changes, summary is that of ba_solve on an empty window, the return value is 0.
+ * summary, ba_iteration_log, ba_last_prepare and the plan cache describe the sub-window: a repeat with the same
+ * selection reuses the plan. */
+int32_t ba_solve_local(ba_context* ctx, ba_problem* prob, const ba_local_request* req, ba_local_info* info,
+                       ba_summary* summary);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the

@@ -8,6 +8,9 @@
  *    SURF/ORB, tracking) can be replayed bit-for-bit on a GPU box that has none of it.
  *    Capture needs no code change: with MIBA_DUMP_DIR set in the environment, every
  *    ba_solve() / ba_prepare() first writes its window to $MIBA_DUMP_DIR/window_<pid>_<n>.miba.
+ *    A dump does not carry the context's constant cameras (ba_set_constant_cameras): a window
+ *    solved under such a set replays with fixed_cam as its only constant pose unless the replaying
+ *    program sets the same mask again. (ba_solve_local dumps its sub-window, without the mask.)
  *
  *    Layout (little endian, every array 8-byte aligned):
  *      off   0  char     magic[8] = "MIBAWIN1"
