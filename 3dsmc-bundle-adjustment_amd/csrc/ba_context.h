@@ -99,6 +99,9 @@ enum BufId {
     B_DP_CONST,
     // ba_local_window (allocated on its first call): the integer scratch of the selection and its outputs
     B_LOCAL_WORK, B_LOCAL_OUT,
+    // ba_localize (allocated on its first call): its own copy of the window (poses, points, intrinsics, observation
+    // values), the grouped observation indices with the workgroups' records, and the statistics and log it writes
+    B_LOC_IN, B_LOC_IDX, B_LOC_OUT,
     B_COUNT
 };
 
@@ -185,6 +188,7 @@ struct ba_context {
         std::vector<uint8_t> cam_constant, is_local;  // per sub-window camera: constant; a member of L
     } local;
     hipEvent_t local_ev[2] = {nullptr, nullptr};  // ba_local_window's events around its kernels (first call)
+    hipEvent_t loc_ev[2] = {nullptr, nullptr};    // ba_localize's events around its kernel (first call)
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
     int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout

@@ -378,6 +378,55 @@ class BaLocalInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+LOC_STAT_N = 8  # BA_LOC_STAT_N
+LOC_STAT_FIELDS = ("n_obs", "initial_cost", "final_cost", "iterations", "successful_steps", "unsuccessful_steps",
+                   "termination_type", "message_kind")
+
+
+class BaLocRequest(C.Structure):
+    """Mirror of ``ba_loc_request`` (ba_localize). ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("cam_mask", _u8p),
+        ("cam_stats", _dp),
+        ("log_cam", C.c_int32),
+        ("log_max_rows", C.c_int32),
+        ("log_rows", _dp),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaLocInfo(C.Structure):
+    """Mirror of ``ba_loc_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_selected", C.c_int32),
+        ("n_solved", C.c_int32),
+        ("n_convergence", C.c_int32),
+        ("n_no_convergence", C.c_int32),
+        ("n_failure", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("log_rows", C.c_int32),
+        ("time_lm_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaCovisInfo,
-                   BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest,
+                   BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest, BaLocInfo, BaLocRequest, LOC_STAT_N,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -172,6 +172,40 @@ class Solver:
         d = s.as_dict()
         d["window"] = win
         return d
+
+    def localize(self, prob: ProblemArrays, cams=None, log_cam=None) -> dict:
+        """ba_localize: refine the poses of the cameras ``cams`` (indices or a boolean mask of n_cams entries; ``None``:
+        every camera) against the points and intrinsics of ``prob`` as they stand, each camera on its own
+        observations alone. ``prob.cams`` is updated in place; nothing else in ``prob`` changes and the context's plan
+        and LM state are not touched. Returns the fields of ``ba_loc_info``, ``stats`` (n_cams, 8) (see
+        ``capi.LOC_STAT_FIELDS``; a camera that was not selected or has no admissible observation has stats[6] = -1)
+        and ``log``: camera ``log_cam``'s iteration rows (``iteration_log``'s layout), ``None`` without ``log_cam``."""
+        req, info = BaLocRequest(), BaLocInfo()
+        nc = prob.n_cams
+        if cams is not None:
+            c = np.asarray(cams)
+            if c.dtype == bool:
+                if c.shape != (nc,):
+                    raise ValueError("a boolean camera mask must have one entry per camera")
+                mask = np.ascontiguousarray(c, dtype=np.uint8)
+            else:
+                mask = np.zeros(nc, dtype=np.uint8)
+                mask[np.asarray(c, dtype=np.int64).reshape(-1)] = 1
+            if nc:
+                req.cam_mask = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        stats = np.zeros((max(nc, 1), LOC_STAT_N))
+        req.cam_stats = _dptr(stats)
+        req.log_cam = -1
+        log = None
+        if log_cam is not None:
+            log = np.zeros((max(int(self.options.max_num_iterations), 0) + 1, _lib.LOG_WIDTH))
+            req.log_cam, req.log_max_rows, req.log_rows = int(log_cam), log.shape[0], _dptr(log)
+        ps = prob.struct()
+        self._check(self._L.ba_localize(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_localize")
+        out = info.as_dict()
+        out["stats"] = stats[:nc]
+        out["log"] = None if log is None else log[: min(info.log_rows, log.shape[0])].copy()
+        return out
 
     @staticmethod
     def comm_unique_id() -> bytes:

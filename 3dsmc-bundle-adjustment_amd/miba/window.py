@@ -126,6 +126,48 @@ def local_optimize(kf_c: int, keyframes: list, landmarks: dict, intr_init, intr_
                            lambda prob: solve_local(prob, kf_c, min_weight=min_weight, max_local=max_local))
 
 
+def localize_frame(k: int, keyframes: list, landmarks: dict, intr, seen=None):
+    """Keyframe ``k`` against the map as one-camera ``ProblemArrays`` (``None`` when nothing qualifies): its admissible
+    observations of the landmarks an earlier keyframe (index < k) also observes, in the order of its
+    global_points_map. A landmark first seen by ``k`` was created from k's own pose and says nothing about it.
+    ``seen``: the landmark ids keyframes 0 .. k-1 observe, for a caller that keeps that set as the sequence grows
+    (run_pipeline); ``None``: collected here."""
+    kf = keyframes[k]
+    if seen is None:
+        seen = set()
+        for other in keyframes[:k]:
+            seen.update(other.global_points_map.values())
+    obs_pt, uv, depth, pts, pt_index = [], [], [], [], {}
+    for local_id, landmark_id in kf.global_points_map.items():
+        d = float(kf.points3d_local[local_id][2])
+        if d <= 1e-15 or landmark_id not in seen:
+            continue
+        if landmark_id not in pt_index:
+            pt_index[landmark_id] = len(pts)
+            pts.append(np.array(landmarks[landmark_id], dtype=np.float64))
+        obs_pt.append(pt_index[landmark_id])
+        uv.append((float(kf.keypoints[local_id][0]), float(kf.keypoints[local_id][1])))
+        depth.append(d)
+    if not obs_pt:
+        return None
+    K = np.array(intr, dtype=np.float64)
+    return ProblemArrays(np.array(kf.T_w_c, dtype=np.float64).reshape(1, 7), np.array(pts).reshape(-1, 3), K, K.copy(),
+                         np.zeros(len(obs_pt), dtype=np.int32), np.array(obs_pt, dtype=np.int32),
+                         np.array(uv, dtype=np.float64).reshape(-1, 2), np.array(depth, dtype=np.float64), fixed_cam=-1)
+
+
+def localize_keyframe(k: int, keyframes: list, landmarks: dict, intr, localize, seen=None):
+    """Pose-only refinement of keyframe ``k`` against the map as it stands ("track local map"): ``localize_frame``
+    handed to ``localize`` -- a ``miba.solver.Solver().localize`` -- and the pose written back. Landmarks and
+    intrinsics are constant. With no landmark shared with an earlier keyframe it does nothing and returns ``None``."""
+    prob = localize_frame(k, keyframes, landmarks, intr, seen)
+    if prob is None:
+        return None
+    out = localize(prob)
+    keyframes[k].T_w_c = prob.cams[0].copy()
+    return out
+
+
 def window_schedule(frame_frequency: int, window_size: int, n_keyframes: int, tracking_finished: bool,
                     optimization_finished: bool, tracked_this_frame: bool):
     """(run, kf_i, kf_f, finishes) for main.cpp:163-183."""

@@ -55,7 +55,9 @@ extern "C" {
  *   2, additive  ba_covisibility with ba_covis_request / ba_covis_info (both sized structs) and ba_solve_ordered;
  *                nothing else changed.
  *   2, additive  ba_set_constant_cameras (a set of constant poses beside fixed_cam), ba_local_window with
- *                ba_local_request / ba_local_info (both sized structs) and ba_solve_local; nothing else changed. */
+ *                ba_local_request / ba_local_info (both sized structs) and ba_solve_local; nothing else changed.
+ *   2, additive  ba_localize with ba_loc_request / ba_loc_info (both sized structs): pose-only refinement of keyframes
+ *                against a constant map; ba_options and everything else unchanged. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -515,6 +517,68 @@ int32_t ba_local_window(ba_context* ctx, const ba_problem* prob, const ba_local_
  * selection reuses the plan. */
 int32_t ba_solve_local(ba_context* ctx, ba_problem* prob, const ba_local_request* req, ba_local_info* info,
                        ba_summary* summary);
+
+/* ---- localisation: pose-only refinement against a constant map ----
+ * The optimiser a SLAM front-end calls per frame (ORB-SLAM's "track local map") or per pose hypothesis
+ * (relocalisation): every selected camera's pose is refined with the points and the intrinsics held constant. With
+ * those constant the cameras decouple, so a call is a batch of independent 6-parameter problems, one workgroup each,
+ * the whole trust-region loop inside one kernel launch.
+ * Cost. For every selected camera c with at least one admissible observation (depth > 1e-15) the call minimises over
+ * c's pose alone the cost ba_solve has on the one-camera window made of c's observations: the sum over c's admissible
+ * observations of 0.5 rho_repr + 0.5 rho_unpr with the weights 1 / N_c and weight_unpr / N_c, N_c being c's OWN
+ * admissible count, and the Huber parameters of the context's options. The IntrinsicsPrior block has only constant
+ * parameters and is not part of the cost (Ceres drops such a block from the program).
+ * Loop. The LM loop of ba_solve restated per camera, every option taken from the context's ba_options: Jacobi scaling
+ * 1 / (1 + sqrt(column norm^2)) taken at iteration 0; the LM diagonal clamp(diag, min_lm_diagonal, max_lm_diagonal) /
+ * radius; the step delta = -scale * y applied as T * exp(delta); the model cost change from the unscaled Jacobian; rho
+ * against min_relative_decrease; the radius update and the decrease factor; a non-positive or non-finite Cholesky
+ * pivot or a model cost change that is not positive is an invalid step, max_num_consecutive_invalid_steps of them end
+ * the camera with BA_FAILURE; the gradient, parameter and function tolerances, |x| being the ambient norm of the one
+ * pose (7 values); max_num_iterations. log_rows receives camera log_cam's rows in ba_iteration_log's layout (the
+ * gradient max-norm column is filled in every row).
+ * cam_stats, BA_LOC_STAT_N values per camera of the window:
+ *   [0] admissible observations N_c   [1] initial cost            [2] final cost (the lowest cost of any iteration)
+ *   [3] LM iterations                 [4] successful steps (Ceres convention: includes iteration 0)
+ *   [5] unsuccessful steps            [6] termination type (BA_CONVERGENCE / BA_NO_CONVERGENCE / BA_FAILURE), or -1 for
+ *   a camera that was not selected or has no admissible observation   [7] the message kind of the LM loop (the msg of
+ *   ba_debug_step_state). A camera with [6] = -1 has zeros elsewhere.
+ *   [2] follows ceres::Solver::Summary::final_cost: the lowest cost any iteration evaluated, a rejected candidate's
+ *   included, so it can lie below the cost at the returned pose (the cost of the last successful step in the log).
+ * Inputs. prob->fixed_cam and the context's constant set (ba_set_constant_cameras) are not consulted: cam_mask alone
+ * says which cameras are localised.
+ * Outputs. Selected cameras are updated in place; points, intrinsics, the observation arrays and the unselected
+ * cameras stay bitwise untouched, and so does a selected camera without an admissible observation. A camera whose
+ * evaluation at the given pose is not finite ends with BA_FAILURE and keeps its pose.
+ * Stand-alone like ba_covisibility: validates the window as ba_prepare does, works on device buffers of its own (the
+ * context keeps them between calls) and touches neither the context's plan nor its LM state: a ba_solve_prepared
+ * after it is bitwise the solve without it.
+ * Reproducibility. No floating-point atomics; every sum has one fixed order, set by the observation's position among
+ * its camera's admissible observations in the caller's order, and a camera's result does not depend on what else is
+ * in the call: alone or beside hundreds of other cameras it gives the same bits.
+ * ba_loc_info: n_selected cameras the mask names, n_solved of them with an admissible observation (the grid),
+ * n_convergence + n_no_convergence + n_failure = n_solved, max_iterations the most LM iterations any camera took,
+ * log_rows the rows camera log_cam's loop produced (iterations + 1, of which the first min(log_rows, log_max_rows) are
+ * written and the rest of the buffer is left alone; 0 when log_cam was not solved or its evaluation at the given pose
+ * failed).
+ * log_cam >= n_cams, log_max_rows > 0 without log_rows, contexts with landmark shards: BA_E_INVALID. */
+#define BA_LOC_STAT_N 8
+typedef struct ba_loc_request {
+    int32_t struct_size, reserved0;      /* BA_LOC_REQUEST_INIT */
+    const uint8_t* cam_mask;             /* optional [n_cams]: non-zero = localise this camera; NULL = every camera */
+    double* cam_stats;                   /* optional [n_cams * BA_LOC_STAT_N] */
+    int32_t log_cam, log_max_rows;       /* log_cam < 0: no log */
+    double* log_rows;                    /* [log_max_rows * BA_LOG_WIDTH], rows as ba_iteration_log, of camera log_cam */
+} ba_loc_request;
+typedef struct ba_loc_info {
+    int32_t struct_size, n_selected, n_solved, n_convergence, n_no_convergence, n_failure, max_iterations, log_rows;
+    double time_lm_ms, time_total_ms;    /* the kernel (HIP events); the whole call */
+} ba_loc_info;
+#define BA_LOC_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_loc_request))
+#define BA_LOC_INFO_MIN_SIZE ((int32_t)sizeof(ba_loc_info))
+/* (a zeroed request names camera 0 with log_max_rows = 0: no row is written, ba_loc_info.log_rows counts camera 0's) */
+#define BA_LOC_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_LOC_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_localize(ba_context* ctx, ba_problem* prob, const ba_loc_request* req, ba_loc_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the
