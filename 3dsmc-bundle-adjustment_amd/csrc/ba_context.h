@@ -1,7 +1,9 @@
 // ba_context.h — the libmiba context and what its host translation units share (internal).
 //
-// ba_solver.cpp: the C-ABI surface and the LM loop; ba_prepare.cpp: ba_prepare's phases (staging, plan, device
-// structure, plan cache); ba_debug.cpp: the ba_debug_* entry points.
+// ba_solver.cpp: the C-ABI core and the LM loop; ba_prepare.cpp: ba_prepare's phases (staging, plan, device
+// structure, plan cache); ba_debug.cpp: the ba_debug_* entry points. The stages beside the LM loop, one file each on
+// the scaffold of ba_stage.h: ba_cov.cpp (ba_covariance), ba_resid.cpp (ba_residuals), ba_covis.cpp (ba_covisibility,
+// ba_solve_ordered), ba_local.cpp (ba_local_window, ba_solve_local), ba_loc.cpp (ba_localize).
 #pragma once
 #include <hip/hip_runtime.h>
 

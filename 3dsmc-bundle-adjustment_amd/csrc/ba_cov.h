@@ -6,8 +6,8 @@
 
 namespace miba {
 
-// block size of the dense inverse (the BCR's 64x64 LDS factor)
-static constexpr int COV_B = 64;
+// block size of the dense inverse: the blocked Cholesky's (ba_dense.h), the two share the tile kit of ba_tile64.h
+static constexpr int COV_B = DENSE_B;
 inline int cov_nblk(int n) { return (n + COV_B - 1) / COV_B; }
 
 // Device status of one ba_covariance call: flag != 0 once a pivot was <= 0 or not finite (every later launch

@@ -23,64 +23,18 @@
 #include "ba_device.h"
 #include "ba_kernels.h"
 #include "ba_tail.h"
+#include "ba_tile64.h"
 
 namespace miba {
 
 namespace {
 
-typedef double cov_d4 __attribute__((ext_vector_type(4)));
 constexpr int CB = COV_B;
 constexpr int CTPB = 256;    // 4 waves: one 32x32 quad each
 constexpr int CLD = CB + 1;  // LDS row stride of a staged block
 
 __device__ __forceinline__ bool cov_rank_bad(const CovStat* st, double rcond) {
     return st->flag != 0 || !(st->pmin / st->pmax >= rcond);
-}
-
-// acc[ti][tj] += sum_k A(16 ti + r, k) B(16 tj + c, k), k in [0, K), K a multiple of 4;
-// A(i, k) = A[i * sai + k * sak], B(j, k) = B[j * sbj + k * sbk].
-// f64 MFMA lane map: lane l feeds A(row l & 15, k = l >> 4) and B(col l & 15, k = l >> 4) per k-step of 4, and
-// holds the results (row (l >> 4) + 4 g, col l & 15) in element g.
-__device__ __forceinline__ void quad_mma(cov_d4 (&acc)[2][2], const double* __restrict__ A, size_t sai, size_t sak,
-                                         const double* __restrict__ B, size_t sbj, size_t sbk, int K) {
-    const int lane = threadIdx.x & 63, rr = lane & 15, kk = lane >> 4;
-    const double* a0 = A + rr * sai + kk * sak;
-    const double* a1 = a0 + 16 * sai;
-    const double* b0 = B + rr * sbj + kk * sbk;
-    const double* b1 = b0 + 16 * sbj;
-    const size_t da = 4 * sak, db = 4 * sbk;
-    for (int s = 0; s < K; s += 4) {
-        const double x0 = *a0, x1 = *a1, y0 = *b0, y1 = *b1;
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y1, acc[1][1], 0, 0, 0);
-        a0 += da; a1 += da; b0 += db; b1 += db;
-    }
-}
-
-__device__ __forceinline__ void quad_zero(cov_d4 (&acc)[2][2]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = cov_d4{0.0, 0.0, 0.0, 0.0};
-}
-
-// C(row, col) of the wave's quad (qi, qj) within a 64x64 block at C (leading dimension ld): C = sgn * acc (+ C)
-template <bool ADD>
-__device__ __forceinline__ void quad_store(const cov_d4 (&acc)[2][2], double* __restrict__ C, size_t ld, int qi, int qj,
-                                           double sgn) {
-    const int lane = threadIdx.x & 63, rr = lane & 15, kk = lane >> 4;
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                double* p = C + (size_t)(32 * qi + 16 * ti + kk + 4 * g) * ld + 32 * qj + 16 * tj + rr;
-                if constexpr (ADD) *p += sgn * acc[ti][tj][g];
-                else *p = sgn * acc[ti][tj][g];
-            }
 }
 
 __global__ __launch_bounds__(CTPB) void k_cov_copy(const double* __restrict__ S, int lds, int n, double* __restrict__ A,
@@ -101,11 +55,8 @@ __global__ __launch_bounds__(CTPB) void k_cov_copy(const double* __restrict__ S,
 }
 
 // One workgroup: the diagonal block's Cholesky factor (into A_kk) and its inverse (into Z_kk, zeros above the
-// diagonal) in one elimination: the row operations that reduce A_kk to L^T, applied to the identity, leave L^-1
-// (L^-1 [A | I] = [L^T | L^-1]). Column j: l_ij = a_ij / sqrt(d), row j of X scaled by 1 / sqrt(d); then row i > j
-// subtracts l_ij times row j over its i + 1 live entries: columns c <= j of X, columns j < c <= i of the lower
-// triangle of A. Two barriers per column; the pivot is read by every thread, so a failure exits uniformly.
-// Pivots of the padded rows (>= n, exactly 1) do not count for the extrema.
+// diagonal) in one elimination (tile_chol_inv, ba_tile64.h). Pivots of the padded rows (>= n, exactly 1) do not count
+// for the extrema; a failing pivot does (the extrema are taken before it is judged).
 __global__ __launch_bounds__(CTPB) void k_cov_diag(double* __restrict__ A, double* __restrict__ Zm, int ld, int k, int n,
                                                    CovStat* __restrict__ stat) {
     if (stat->flag) return;
@@ -121,32 +72,10 @@ __global__ __launch_bounds__(CTPB) void k_cov_diag(double* __restrict__ A, doubl
     }
     for (int e = tid; e < CB * (CB + 1) / 2; e += CTPB) Xs[e] = 0.0;
     double pmin = stat->pmin, pmax = stat->pmax;
-    bool bad = false;
     __syncthreads();
-    const int ri = tid & (CB - 1), cg = tid >> 6;  // phase 2: row ri, columns cg, cg + 4, ...
-    for (int j = 0; j < CB; ++j) {
-        const double d = Ls[j * CLD + j];  // (not written during the elimination: diag(L) goes to Dg)
+    const bool bad = tile_chol_inv<CTPB, CLD, true>(Ls, Xs, Dg, [&](int j, double d) __attribute__((always_inline)) {
         if (k * CB + j < n) { pmin = fmin(pmin, d); pmax = fmax(pmax, d); }
-        if (!(d > 0.0) || !isfinite(d)) { bad = true; break; }
-        const double sd = sqrt(d), inv = 1.0 / sd;
-        if (tid < CB) {
-            if (tid > j) Ls[tid * CLD + j] *= inv;
-            else if (tid == j) Dg[j] = sd;
-        } else if (tid < 2 * CB) {
-            const int c = tid - CB;
-            if (c < j) Xs[j * (j + 1) / 2 + c] *= inv;
-            else if (c == j) Xs[j * (j + 1) / 2 + j] = inv;
-        }
-        __syncthreads();
-        if (ri > j) {
-            const double lij = Ls[ri * CLD + j];
-            for (int c = cg; c <= ri; c += CTPB / CB) {
-                if (c <= j) Xs[ri * (ri + 1) / 2 + c] -= lij * Xs[j * (j + 1) / 2 + c];
-                else Ls[ri * CLD + c] -= lij * Ls[c * CLD + j];
-            }
-        }
-        __syncthreads();
-    }
+    });
     if (bad) {
         if (tid == 0) {
             stat->flag = 1;
@@ -177,13 +106,12 @@ __global__ __launch_bounds__(CTPB) void k_cov_panel(double* __restrict__ A, doub
                        : Zm + ((size_t)k * CB) * ld + (size_t)(b - nl) * CB;
     for (int e = tid; e < CB * CB; e += CTPB) T[(e / CB) * CLD + e % CB] = X[(size_t)(e / CB) * ld + e % CB];
     __syncthreads();
-    cov_d4 acc[2][2];
-    quad_zero(acc);
+    d4 acc[2][2] = {};
     if (b < nl)  // C(i, j) = sum_m T(i, m) Zkk(j, m)
-        quad_mma(acc, T + 32 * qi * CLD, CLD, 1, Zkk + (size_t)(32 * qj) * ld, ld, 1, CB);
+        tile_mma(acc, T + 32 * qi * CLD, CLD, 1, Zkk + (size_t)(32 * qj) * ld, ld, 1, CB);
     else  // C(i, j) = sum_m Zkk(i, m) T(m, j)
-        quad_mma(acc, Zkk + (size_t)(32 * qi) * ld, ld, 1, T + 32 * qj, 1, CLD, CB);
-    quad_store<false>(acc, X, ld, qi, qj, 1.0);
+        tile_mma(acc, Zkk + (size_t)(32 * qi) * ld, ld, 1, T + 32 * qj, 1, CLD, CB);
+    tile_store<TILE_SET>(acc, X, ld, qi, qj);
 }
 
 // Workgroup (x = j, y = i - (k + 1)), j <= i: j > k: A_ij -= L_ik L_jk^T; j <= k: B_ij -= L_ik Z_kj.
@@ -194,16 +122,15 @@ __global__ __launch_bounds__(CTPB) void k_cov_trail(double* __restrict__ A, doub
     if (j > i) return;
     const int wave = threadIdx.x >> 6, qi = wave >> 1, qj = wave & 1;
     const double* Lik = A + ((size_t)i * CB + 32 * qi) * ld + (size_t)k * CB;
-    cov_d4 acc[2][2];
-    quad_zero(acc);
+    d4 acc[2][2] = {};
     if (j > k) {
         const double* Ljk = A + ((size_t)j * CB + 32 * qj) * ld + (size_t)k * CB;
-        quad_mma(acc, Lik, ld, 1, Ljk, ld, 1, CB);
-        quad_store<true>(acc, A + ((size_t)i * CB) * ld + (size_t)j * CB, ld, qi, qj, -1.0);
+        tile_mma(acc, Lik, ld, 1, Ljk, ld, 1, CB);
+        tile_store<TILE_SUB>(acc, A + ((size_t)i * CB) * ld + (size_t)j * CB, ld, qi, qj);
     } else {
         const double* Zkj = Zm + ((size_t)k * CB) * ld + (size_t)j * CB + 32 * qj;
-        quad_mma(acc, Lik, ld, 1, Zkj, 1, ld, CB);
-        quad_store<true>(acc, Zm + ((size_t)i * CB) * ld + (size_t)j * CB, ld, qi, qj, -1.0);
+        tile_mma(acc, Lik, ld, 1, Zkj, 1, ld, CB);
+        tile_store<TILE_SUB>(acc, Zm + ((size_t)i * CB) * ld + (size_t)j * CB, ld, qi, qj);
     }
 }
 
@@ -217,10 +144,9 @@ __global__ __launch_bounds__(CTPB) void k_cov_ztz(double* __restrict__ A, const 
     const int wave = threadIdx.x >> 6, qi = wave >> 1, qj = wave & 1;
     const double* Zi = Zm + ((size_t)i * CB) * ld + (size_t)i * CB + 32 * qi;
     const double* Zj = Zm + ((size_t)i * CB) * ld + (size_t)j * CB + 32 * qj;
-    cov_d4 acc[2][2];
-    quad_zero(acc);
-    quad_mma(acc, Zi, 1, ld, Zj, 1, ld, (nblk - i) * CB);
-    quad_store<false>(acc, A + ((size_t)i * CB) * ld + (size_t)j * CB, ld, qi, qj, 1.0);
+    d4 acc[2][2] = {};
+    tile_mma(acc, Zi, 1, ld, Zj, 1, ld, (nblk - i) * CB);
+    tile_store<TILE_SET>(acc, A + ((size_t)i * CB) * ld + (size_t)j * CB, ld, qi, qj);
 }
 
 // Cv(i, j) = Cv(j, i) = s_hi * A(hi, lo) * s_lo for i, j < n (the same expression on both sides of the diagonal)

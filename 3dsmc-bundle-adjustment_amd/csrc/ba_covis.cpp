@@ -2,24 +2,29 @@
 // (kernels of ba_covis.hip), the camera order that narrows its band (ba_order.cpp) and the solve in that order.
 // ba_covisibility is a stage beside the LM loop: device buffers of its own, nothing the plan or the LM loop reads is
 // written. ba_solve_ordered is ba_solve on a shadow problem the context keeps.
-#include "ba_context.h"
 #include "ba_covis.h"
 #include "ba_order.h"
+#include "ba_stage.h"
 
 using namespace miba;
 
-namespace {
-
-// ba_prepare's verdict on the sizes and buffers this call reads, then on every observation's indices (the kernels
-// index with them unchecked).
-const char* covis_validate(const ba_problem* p) {
-    if (p->n_cams < 0 || p->n_points < 0 || p->n_obs < 0) return "invalid problem sizes";
-    if (p->n_obs && (!p->obs_cam || !p->obs_pt || !p->obs_depth)) return "null problem buffer";
-    for (int32_t k = 0; k < p->n_obs; ++k)
-        if (p->obs_cam[k] < 0 || p->obs_cam[k] >= p->n_cams || p->obs_pt[k] < 0 || p->obs_pt[k] >= p->n_points)
-            return "observation index out of range";
-    return "";
+int32_t miba::covis_upload_bits(const Stage& stg, const ba_problem* p, hipEvent_t start, CovisBits& b) {
+    ba_context* ctx = stg.ctx;
+    const size_t nc = (size_t)p->n_cams, no = (size_t)p->n_obs;
+    b.dep = ctx->buf[B_COVIS_OBS].as<double>();
+    b.cam = reinterpret_cast<int*>(b.dep + no);
+    b.pt = b.cam + no;
+    b.bits = ctx->buf[B_COVIS_BITS].as<unsigned long long>();
+    HIPCHECK(ctx, stg.h2d(b.dep, p->obs_depth, sizeof(double) * no));
+    HIPCHECK(ctx, stg.h2d(b.cam, p->obs_cam, sizeof(int32_t) * no));
+    HIPCHECK(ctx, stg.h2d(b.pt, p->obs_pt, sizeof(int32_t) * no));
+    HIPCHECK(ctx, hipEventRecord(start, stg.s));
+    HIPCHECK(ctx, hipMemsetAsync(b.bits, 0, covis_bits_bytes(nc, covis_row_words(p->n_points)), stg.s));
+    HIPCHECK(ctx, launch_covis_bits(b.cam, b.pt, b.dep, p->n_obs, p->n_points, b.bits, stg.s));
+    return BA_OK;
 }
+
+namespace {
 
 // a camera's position among the first n_active entries of `order` (-1: the gauge camera / no admissible observation)
 void positions(const int32_t* order, int n_active, int n_cams, int32_t* pos) {
@@ -32,61 +37,38 @@ void positions(const int32_t* order, int n_active, int n_cams, int32_t* pos) {
 extern "C" int32_t ba_covisibility(ba_context* ctx, const ba_problem* p, const ba_covis_request* req,
                                    ba_covis_info* info) {
     if (!ctx) { miba_set_error("null context"); return BA_E_INVALID; }
-    auto invalid = [&](const std::string& m) { ctx->err = "ba_covisibility: " + m; return (int32_t)BA_E_INVALID; };
-    if (!p || !req || !info) return invalid("null argument");
-    if (req->struct_size < BA_COVIS_REQUEST_MIN_SIZE)
-        return invalid("request struct_size below BA_COVIS_REQUEST_MIN_SIZE (set it with BA_COVIS_REQUEST_INIT)");
-    if (info->struct_size < BA_COVIS_INFO_MIN_SIZE)
-        return invalid("info struct_size below BA_COVIS_INFO_MIN_SIZE (set it with BA_COVIS_INFO_INIT)");
-    if (ctx->W.comm.on() || ctx->comm_parked.on())
-        return invalid("contexts with landmark shards (ba_comm_init*) are not supported");
+    const Stage stg{ctx, "ba_covisibility", ctx->stream};
+    if (const std::string m = stage_refusal(ctx, p, req, info, STAGE_SIZES(BA_COVIS)); !m.empty()) return stg.invalid(m);
     const double t0 = now_ms();
-    if (const char* m = covis_validate(p); *m) return invalid(m);
+    if (const char* m = stage_validate_problem(p, STAGE_OBS); *m) return stg.invalid(m);
     HIPCHECK(ctx, hipSetDevice(ctx->device));
-    for (auto& e : ctx->covis_ev)
-        if (!e) HIPCHECK(ctx, hipEventCreate(&e));
-    hipStream_t s = ctx->stream;
+    HIPCHECK(ctx, stg.events(ctx->covis_ev, 2));
+    hipStream_t s = stg.s;
     const size_t nc = (size_t)p->n_cams, np = (size_t)p->n_points, no = (size_t)p->n_obs;
     const size_t nw = covis_row_words(p->n_points);
 
     // depths | camera indices | point indices; the bit matrix; the weights; positions (2 nc) | spans (4 np) | counts (2)
-    auto nomem = [&](const char* what, size_t bytes) {
-        (void)hipGetLastError();
-        ctx->err = std::string("ba_covisibility: cannot allocate ") + what + " (" + std::to_string(bytes) + " bytes)";
-        return (int32_t)BA_E_NOMEM;
-    };
-    const size_t obs_bytes = 16 * std::max<size_t>(no, 1), bits_bytes = 8 * std::max<size_t>(nc * nw, 1);
+    const size_t obs_bytes = covis_obs_bytes(no), bits_bytes = covis_bits_bytes(nc, nw);
     const size_t w_bytes = 4 * std::max<size_t>(nc * nc, 1), span_bytes = 4 * (2 * nc + 4 * np + 2);
-    if (ctx->buf[B_COVIS_OBS].ensure(obs_bytes) != hipSuccess) return nomem("the observation copies", obs_bytes);
-    if (ctx->buf[B_COVIS_BITS].ensure(bits_bytes) != hipSuccess) return nomem("the camera x point bit matrix", bits_bytes);
-    if (ctx->buf[B_COVIS_W].ensure(w_bytes) != hipSuccess) return nomem("the weights", w_bytes);
-    if (ctx->buf[B_COVIS_SPAN].ensure(span_bytes) != hipSuccess) return nomem("the span scratch", span_bytes);
-    double* d_dep = ctx->buf[B_COVIS_OBS].as<double>();
-    int* d_cam = reinterpret_cast<int*>(d_dep + no);
-    int* d_pt = d_cam + no;
-    unsigned long long* d_bits = ctx->buf[B_COVIS_BITS].as<unsigned long long>();
+    if (int32_t rc = stg.ensure(B_COVIS_OBS, obs_bytes, "the observation copies")) return rc;
+    if (int32_t rc = stg.ensure(B_COVIS_BITS, bits_bytes, "the camera x point bit matrix")) return rc;
+    if (int32_t rc = stg.ensure(B_COVIS_W, w_bytes, "the weights")) return rc;
+    if (int32_t rc = stg.ensure(B_COVIS_SPAN, span_bytes, "the span scratch")) return rc;
     int* d_W = ctx->buf[B_COVIS_W].as<int>();
     int* d_pos0 = ctx->buf[B_COVIS_SPAN].as<int>();
     int* d_pos1 = d_pos0 + nc;
     int* d_span = d_pos1 + nc;
     int* d_wide = d_span + 4 * np;
 
-    auto h2d = [&](void* dst, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    HIPCHECK(ctx, h2d(d_dep, p->obs_depth, sizeof(double) * no));
-    HIPCHECK(ctx, h2d(d_cam, p->obs_cam, sizeof(int32_t) * no));
-    HIPCHECK(ctx, h2d(d_pt, p->obs_pt, sizeof(int32_t) * no));
-    HIPCHECK(ctx, hipEventRecord(ctx->covis_ev[0], s));
-    HIPCHECK(ctx, hipMemsetAsync(d_bits, 0, bits_bytes, s));
+    CovisBits cb{};
+    if (int32_t rc = covis_upload_bits(stg, p, ctx->covis_ev[0], cb)) return rc;
     HIPCHECK(ctx, hipMemsetAsync(d_W, 0, w_bytes, s));
-    HIPCHECK(ctx, launch_covis_bits(d_cam, d_pt, d_dep, p->n_obs, p->n_points, d_bits, s));
-    HIPCHECK(ctx, launch_covis_count(d_bits, p->n_cams, p->n_points, d_W, s));
+    HIPCHECK(ctx, launch_covis_count(cb.bits, p->n_cams, p->n_points, d_W, s));
     HIPCHECK(ctx, hipEventRecord(ctx->covis_ev[1], s));
     std::vector<int32_t> W_tmp;
     int32_t* W = req->weights;
     if (!W) { W_tmp.resize(std::max<size_t>(nc * nc, 1)); W = W_tmp.data(); }
-    if (nc) HIPCHECK(ctx, hipMemcpyAsync(W, d_W, sizeof(int32_t) * nc * nc, hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, stg.d2h(W, d_W, sizeof(int32_t) * nc * nc));
     HIPCHECK(ctx, hipStreamSynchronize(s));
 
     // the candidate order on the host, then what it does to the points' spans on the device
@@ -95,8 +77,8 @@ extern "C" int32_t ba_covisibility(ba_context* ctx, const ba_problem* p, const b
     // the context's constant cameras count as the gauge camera does (a mask set for another n_cams: BA_E_INVALID, as
     // a prepare of this window would say)
     if (ctx->cmask_any && ctx->cmask.size() != nc)
-        return invalid("the window has " + std::to_string(p->n_cams) + " cameras, the constant-camera mask was set for " +
-                       std::to_string(ctx->cmask.size()));
+        return stg.invalid("the window has " + std::to_string(p->n_cams) +
+                           " cameras, the constant-camera mask was set for " + std::to_string(ctx->cmask.size()));
     const uint8_t* cam_const = ctx->cmask_any ? ctx->cmask.data() : nullptr;
     covis_order(W, p->n_cams, p->fixed_cam, cam_const, co);
     std::vector<int32_t> pos(2 * nc), given;
@@ -105,9 +87,9 @@ extern "C" int32_t ba_covisibility(ba_context* ctx, const ba_problem* p, const b
     positions(given.data(), co.n_active, p->n_cams, pos.data());
     positions(co.order.data(), co.n_active, p->n_cams, pos.data() + nc);
     int32_t wide[2] = {0, 0};
-    HIPCHECK(ctx, h2d(d_pos0, pos.data(), sizeof(int32_t) * 2 * nc));
-    HIPCHECK(ctx, launch_covis_span(d_cam, d_pt, d_dep, p->n_obs, p->n_points, d_pos0, d_pos1, TILE_WIN, d_span, d_wide, s));
-    HIPCHECK(ctx, hipMemcpyAsync(wide, d_wide, sizeof(wide), hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx, stg.h2d(d_pos0, pos.data(), sizeof(int32_t) * 2 * nc));
+    HIPCHECK(ctx, launch_covis_span(cb.cam, cb.pt, cb.dep, p->n_obs, p->n_points, d_pos0, d_pos1, TILE_WIN, d_span, d_wide, s));
+    HIPCHECK(ctx, stg.d2h(wide, d_wide, sizeof(wide)));
     HIPCHECK(ctx, hipStreamSynchronize(s));
     const bool accept = co.band_after < co.band_before && wide[1] <= wide[0];
     if (req->order)
@@ -128,21 +110,19 @@ extern "C" int32_t ba_covisibility(ba_context* ctx, const ba_problem* p, const b
     full.time_count_ms = ms;
     full.time_order_ms = now_ms() - t_order;
     full.time_total_ms = now_ms() - t0;
-    const int32_t keep = info->struct_size;
-    std::memcpy(info, &full, std::min<size_t>((size_t)keep, sizeof(full)));
-    info->struct_size = keep;
+    sized_copy_out(info, full);
     ctx->err.clear();
     return BA_OK;
 }
 
 extern "C" int32_t ba_solve_ordered(ba_context* ctx, ba_problem* p, const int32_t* order, ba_summary* sum) {
     if (!ctx) { miba_set_error("null context"); return BA_E_INVALID; }
-    auto invalid = [&](const std::string& m) { ctx->err = "ba_solve_ordered: " + m; return (int32_t)BA_E_INVALID; };
-    if (!p || !sum) return invalid("null argument");
-    if (ctx->W.comm.on() || ctx->comm_parked.on())
-        return invalid("contexts with landmark shards (ba_comm_init*) are not supported");
-    if (p->n_cams < 0 || p->n_points < 0 || p->n_obs < 0) return invalid("invalid problem sizes");
-    if ((p->n_cams && !p->cams) || (p->n_obs && !p->obs_cam)) return invalid("null problem buffer");
+    const Stage stg{ctx, "ba_solve_ordered", ctx->stream};
+    if (!p || !sum) return stg.invalid("null argument");
+    // (its own checks: no request / info, and of the buffers only those the shadow problem is built from)
+    if (ctx->W.comm.on() || ctx->comm_parked.on()) return stg.invalid(kStageShards);
+    if (p->n_cams < 0 || p->n_points < 0 || p->n_obs < 0) return stg.invalid(kBadSizes);
+    if ((p->n_cams && !p->cams) || (p->n_obs && !p->obs_cam)) return stg.invalid(kNullBuffer);
     const int nc = p->n_cams;
     ba_context::Ordered& sh = ctx->ordered;
     if (!order) {
@@ -158,8 +138,8 @@ extern "C" int32_t ba_solve_ordered(ba_context* ctx, ba_problem* p, const int32_
     sh.inv.assign((size_t)nc, -1);
     for (int k = 0; k < nc; ++k) {
         const int32_t c = order[k];
-        if (c < 0 || c >= nc) return invalid("order[" + std::to_string(k) + "] = " + std::to_string(c) + " is out of range");
-        if (sh.inv[c] >= 0) return invalid("order repeats camera " + std::to_string(c) + ": not a permutation");
+        if (c < 0 || c >= nc) return stg.invalid("order[" + std::to_string(k) + "] = " + std::to_string(c) + " is out of range");
+        if (sh.inv[c] >= 0) return stg.invalid("order repeats camera " + std::to_string(c) + ": not a permutation");
         sh.inv[c] = k;
     }
     sh.cams.resize((size_t)nc * 7);
@@ -167,7 +147,7 @@ extern "C" int32_t ba_solve_ordered(ba_context* ctx, ba_problem* p, const int32_
     sh.obs_cam.resize((size_t)p->n_obs);
     for (int32_t k = 0; k < p->n_obs; ++k) {
         const int32_t c = p->obs_cam[k];
-        if (c < 0 || c >= nc) return invalid("observation index out of range");
+        if (c < 0 || c >= nc) return stg.invalid(kBadIndex);
         sh.obs_cam[k] = sh.inv[c];
     }
     ba_problem shadow = *p;

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+struct ba_problem;  // include/ba.h
+
 namespace miba {
 
 // k_covis_count: one workgroup takes a COVIS_TILE x COVIS_TILE tile of camera pairs and COVIS_SLICE_WORDS 64-bit
@@ -28,5 +30,15 @@ hipError_t launch_covis_count(const unsigned long long* bits, int n_cams, int n_
 // (lowest / highest position per point and placement), wide[2] receives the two counts.
 hipError_t launch_covis_span(const int* obs_cam, const int* obs_pt, const double* obs_depth, int n_obs, int n_points,
                              const int* pos0, const int* pos1, int tile_win, int* span, int* wide, hipStream_t s);
+
+// The bit matrix of a window on the device, for ba_covisibility and ba_local_window (ba_covis.cpp). The caller has
+// sized B_COVIS_OBS to covis_obs_bytes and B_COVIS_BITS to covis_bits_bytes; the window's depths | camera indices |
+// point indices are uploaded into the first, `start` is recorded (the caller's timed interval opens with the clear),
+// the second is cleared and k_covis_bits run. A BA_* code; the HIP text is in the context's error.
+struct Stage;
+struct CovisBits { double* dep; int *cam, *pt; unsigned long long* bits; };
+inline size_t covis_obs_bytes(size_t n_obs) { return 16 * (n_obs > 1 ? n_obs : 1); }
+inline size_t covis_bits_bytes(size_t n_cams, size_t nw) { return 8 * (n_cams * nw > 1 ? n_cams * nw : 1); }
+int32_t covis_upload_bits(const Stage& stg, const ba_problem* p, hipEvent_t start, CovisBits& b);
 
 }  // namespace miba

@@ -5,6 +5,7 @@
 // cameras see (a point seen twice by a camera is one bit). Everything is integer: bit sets by atomicOr (idempotent),
 // sums by integer atomicAdd, spans by atomicMin / atomicMax, all order-independent.
 #include "ba_covis.h"
+#include "ba_obs.h"
 
 namespace miba {
 
@@ -16,13 +17,11 @@ static_assert(COVIS_TILE * COVIS_TILE == COVIS_TPB, "one thread per camera pair 
 static constexpr int COVIS_LDS_STRIDE = COVIS_SLICE_WORDS + 1;
 static_assert(COVIS_LDS_STRIDE % 2 == 1, "odd row stride: the rows of a panel start on different banks");
 
-__device__ __forceinline__ bool covis_admissible(double depth) { return depth > 1e-15; }
-
 __global__ __launch_bounds__(COVIS_TPB) void k_covis_bits(const int* __restrict__ obs_cam, const int* __restrict__ obs_pt,
                                                           const double* __restrict__ obs_depth, int n_obs, size_t nw,
                                                           unsigned long long* __restrict__ bits) {
     const size_t k = (size_t)blockIdx.x * COVIS_TPB + threadIdx.x;
-    if (k >= (size_t)n_obs || !covis_admissible(obs_depth[k])) return;
+    if (k >= (size_t)n_obs || !obs_admissible(obs_depth[k])) return;
     const unsigned pt = (unsigned)obs_pt[k];
     atomicOr(bits + (size_t)obs_cam[k] * nw + (pt >> 6), 1ull << (pt & 63u));
 }
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(COVIS_TPB) void k_covis_span(const int* __restrict_
                                                           const int* __restrict__ pos0, const int* __restrict__ pos1,
                                                           int* __restrict__ span) {
     const size_t k = (size_t)blockIdx.x * COVIS_TPB + threadIdx.x;
-    if (k >= (size_t)n_obs || !covis_admissible(obs_depth[k])) return;
+    if (k >= (size_t)n_obs || !obs_admissible(obs_depth[k])) return;
     const int cam = obs_cam[k];
     const size_t p = (size_t)obs_pt[k];
     const int a0 = pos0[cam], a1 = pos1[cam];

@@ -11,7 +11,7 @@ namespace miba {
 struct LmState;
 struct Prof;
 
-static constexpr int DENSE_B = 64;  // block size (the covariance's, ba_cov.h)
+static constexpr int DENSE_B = 64;  // block size: the tile of ba_tile64.h (the covariance's COV_B is this one)
 static constexpr int DENSE_BB = DENSE_B * DENSE_B;
 // Default selection: where the solver choice lands on the one-workgroup envelope kernel (k_chol), windows of
 // npad >= BLOCKED_MIN_NPAD take this path instead (measured crossover; MIBA_BLOCKED_MIN overrides).

@@ -20,12 +20,12 @@
 
 #include "ba_dense.h"
 #include "ba_kernels.h"
+#include "ba_tile64.h"
 
 namespace miba {
 
 namespace {
 
-typedef double dn_d4 __attribute__((ext_vector_type(4)));
 constexpr int DB = DENSE_B;
 constexpr int DTPB = 256;   // 4 waves: one 32x32 quad each
 // threads of k_dense_diag: its columns are bound by LDS latency, and 8 waves hide it better than 4 (measured 101 /
@@ -50,38 +50,6 @@ __device__ __forceinline__ void dense_stage(double* __restrict__ T, const double
         *reinterpret_cast<double2*>(T + (e >> 5) * DLD + 2 * (e & 31)) = X2[e];
 }
 
-// acc[ti][tj] += sum_k A(16 ti + r, k) B(16 tj + c, k), k in [0, K), K a multiple of 4; both operands in LDS, row
-// stride DLD. f64 MFMA lane map (quad_mma, ba_cov.hip): lane l feeds A(row l & 15, k = l >> 4) and
-// B(col l & 15, k = l >> 4) per k-step of 4 and holds the results (row (l >> 4) + 4 g, col l & 15) in element g.
-__device__ __forceinline__ void dense_mma(dn_d4 (&acc)[2][2], const double* A, const double* B, int K) {
-    const int lane = threadIdx.x & 63, rr = lane & 15, kk = lane >> 4;
-    const double* a0 = A + rr * DLD + kk;
-    const double* b0 = B + rr * DLD + kk;
-    for (int s = 0; s < K; s += 4) {
-        const double x0 = a0[s], x1 = a0[16 * DLD + s], y0 = b0[s], y1 = b0[16 * DLD + s];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y1, acc[1][1], 0, 0, 0);
-    }
-}
-
-// the wave's quad (qi, qj) of the 64x64 block C (row stride 64): C = acc, or C -= acc
-template <bool SUB>
-__device__ __forceinline__ void dense_store(const dn_d4 (&acc)[2][2], double* __restrict__ C, int qi, int qj) {
-    const int lane = threadIdx.x & 63, rr = lane & 15, kk = lane >> 4;
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                double* p = C + (32 * qi + 16 * ti + kk + 4 * g) * DB + 32 * qj + 16 * tj + rr;
-                if constexpr (SUB) *p -= acc[ti][tj][g];
-                else *p = acc[ti][tj][g];
-            }
-}
-
 // Workgroups [0, n_env): one envelope block each; the last workgroup: the right-hand side.
 __global__ __launch_bounds__(DTPB) void k_dense_copy(const LmState* __restrict__ st, const double* __restrict__ S,
                                                      int npad, const double* __restrict__ rhs, DenseWork D) {
@@ -101,11 +69,9 @@ __global__ __launch_bounds__(DTPB) void k_dense_copy(const LmState* __restrict__
     }
 }
 
-// One workgroup: the diagonal block's Cholesky factor and its inverse in one elimination, as k_cov_diag does
-// (L^-1 [A | I] = [L^T | L^-1]): column j scales by 1 / sqrt(d), then row i > j subtracts l_ij times row j over its
-// i + 1 live entries (NT / 64 threads per row). Two barriers per column; the pivot is read by every thread, so a
-// failure exits uniformly. Only Z_K = L^-1 is kept (the panel, the forward and the backward solve all multiply by
-// it), and z_K = Z_K b_K.
+// One workgroup: the diagonal block's Cholesky factor and its inverse in one elimination (tile_chol_inv,
+// ba_tile64.h, NT / 64 threads per row). Only Z_K = L^-1 is kept (the panel, the forward and the backward solve all
+// multiply by it), and z_K = Z_K b_K.
 // (Measured alternatives, DESIGN §4.9: the rows in registers with one hand-off buffer and one barrier per column ran
 // 1.5x - 2.5x slower at 256 threads: those variants execute every row's 16 entries under predicates where this
 // loop runs the live entries only.)
@@ -124,31 +90,8 @@ __global__ __launch_bounds__(NT) void k_dense_diag(const LmState* __restrict__ s
     }
     for (int e = tid; e < DB * (DB + 1) / 2; e += NT) Xs[e] = 0.0;
     if (tid < DB) bs[tid] = D.bz[DB * K + tid];
-    bool bad = false;
     __syncthreads();
-    const int ri = tid & (DB - 1), cg = tid >> 6;  // elimination: row ri, columns cg, cg + NT / 64, ...
-    for (int j = 0; j < DB; ++j) {
-        const double d = Ls[j * DLDD + j];
-        if (!(d > 0.0) || !isfinite(d)) { bad = true; break; }
-        const double inv = 1.0 / sqrt(d);
-        if (tid < DB) {
-            if (tid > j) Ls[tid * DLDD + j] *= inv;
-        } else if (tid < 2 * DB) {
-            const int c = tid - DB;
-            if (c < j) Xs[j * (j + 1) / 2 + c] *= inv;
-            else if (c == j) Xs[j * (j + 1) / 2 + j] = inv;
-        }
-        __syncthreads();
-        if (ri > j) {
-            const double lij = Ls[ri * DLDD + j];
-            for (int c = cg; c <= ri; c += NT / DB) {
-                if (c <= j) Xs[ri * (ri + 1) / 2 + c] -= lij * Xs[j * (j + 1) / 2 + c];
-                else Ls[ri * DLDD + c] -= lij * Ls[c * DLDD + j];
-            }
-        }
-        __syncthreads();
-    }
-    if (bad) {
+    if (tile_chol_inv<NT, DLDD, false>(Ls, Xs, nullptr, [](int, double) {})) {
         if (tid == 0) *flag |= FLAG_NOT_PD;  // (the only writer between the assembly and k_final on this path)
         return;
     }
@@ -177,10 +120,10 @@ __global__ __launch_bounds__(DTPB) void k_dense_panel(const LmState* __restrict_
     dense_stage(T0, X);
     dense_stage(T1, D.Zd + (size_t)K * DENSE_BB);
     __syncthreads();
-    dn_d4 acc[2][2] = {};
+    d4 acc[2][2] = {};
     // C(i, j) = sum_m X(i, m) Z(j, m); Z is lower triangular: m <= j < 32 (qj + 1)
-    dense_mma(acc, T0 + 32 * qi * DLD, T1 + 32 * qj * DLD, 32 * (qj + 1));
-    dense_store<false>(acc, X, qi, qj);
+    tile_mma(acc, T0 + 32 * qi * DLD, DLD, 1, T1 + 32 * qj * DLD, DLD, 1, 32 * (qj + 1));
+    tile_store<TILE_SET>(acc, X, DB, qi, qj);
 }
 
 // Workgroup (x = q, y = p) with q <= p < nr: A_IJ -= L_IK L_JK^T for I = rows[p], J = rows[q] of column K's list;
@@ -216,9 +159,9 @@ __global__ __launch_bounds__(DTPB) void k_dense_trail(const LmState* __restrict_
     if (p != q) dense_stage(T1, dense_blk(D, J, K));
     __syncthreads();
     if (p == q && qj > qi) return;  // a diagonal block: its lower triangle only
-    dn_d4 acc[2][2] = {};
-    dense_mma(acc, T0 + 32 * qi * DLD, T1 + 32 * qj * DLD, DB);
-    dense_store<true>(acc, dense_blk(D, I, J), qi, qj);
+    d4 acc[2][2] = {};
+    tile_mma(acc, T0 + 32 * qi * DLD, DLD, 1, T1 + 32 * qj * DLD, DLD, 1, DB);
+    tile_store<TILE_SUB>(acc, dense_blk(D, I, J), DB, qi, qj);
 }
 
 // One workgroup: t = z_K - sum over column K's list of L_IK^T y_I (thread (c, part) sums the rows part * 16 .. + 15

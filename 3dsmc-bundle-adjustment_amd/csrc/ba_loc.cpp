@@ -3,9 +3,9 @@
 // ba_loc_group.cpp).
 // A stage beside the LM loop like ba_covisibility and ba_local_window: it works on device buffers of its own
 // (B_LOC_*), so nothing the plan or the LM loop reads is written.
-#include "ba_context.h"
 #include "ba_loc.h"
 #include "ba_loc_group.h"
+#include "ba_stage.h"
 
 #include <cmath>
 
@@ -16,19 +16,8 @@ static_assert(LOC_STAT == BA_LOC_STAT_N && LOG_W == BA_LOG_WIDTH, "the kernel wr
 namespace {
 
 std::string loc_check(ba_context* ctx, const ba_problem* p, const ba_loc_request* req, const ba_loc_info* info) {
-    if (!p || !req || !info) return "null argument";
-    if (req->struct_size < BA_LOC_REQUEST_MIN_SIZE)
-        return "request struct_size below BA_LOC_REQUEST_MIN_SIZE (set it with BA_LOC_REQUEST_INIT)";
-    if (info->struct_size < BA_LOC_INFO_MIN_SIZE)
-        return "info struct_size below BA_LOC_INFO_MIN_SIZE (set it with BA_LOC_INFO_INIT)";
-    if (ctx->W.comm.on() || ctx->comm_parked.on()) return "contexts with landmark shards (ba_comm_init*) are not supported";
-    if (p->n_cams < 0 || p->n_points < 0 || p->n_obs < 0) return "invalid problem sizes";
-    if ((p->n_cams && !p->cams) || (p->n_points && !p->points) || !p->intr || !p->intr_prior ||
-        (p->n_obs && (!p->obs_cam || !p->obs_pt || !p->obs_uv || !p->obs_depth)))
-        return "null problem buffer";
-    for (int32_t k = 0; k < p->n_obs; ++k)
-        if (p->obs_cam[k] < 0 || p->obs_cam[k] >= p->n_cams || p->obs_pt[k] < 0 || p->obs_pt[k] >= p->n_points)
-            return "observation index out of range";
+    if (const std::string m = stage_refusal(ctx, p, req, info, STAGE_SIZES(BA_LOC)); !m.empty()) return m;
+    if (const char* m = stage_validate_problem(p, STAGE_OBS | STAGE_PARAMS); *m) return m;
     if (req->log_cam >= std::max(p->n_cams, 1))  // (a zeroed request, log_cam = 0, is legal on an empty window too)
         return "log_cam = " + std::to_string(req->log_cam) + " is out of range (" + std::to_string(p->n_cams) + " cameras)";
     if (req->log_cam >= 0 && (req->log_max_rows < 0 || (req->log_max_rows > 0 && !req->log_rows)))
@@ -40,10 +29,8 @@ std::string loc_check(ba_context* ctx, const ba_problem* p, const ba_loc_request
 
 extern "C" int32_t ba_localize(ba_context* ctx, ba_problem* p, const ba_loc_request* req, ba_loc_info* info) {
     if (!ctx) { miba_set_error("null context"); return BA_E_INVALID; }
-    if (const std::string m = loc_check(ctx, p, req, info); !m.empty()) {
-        ctx->err = "ba_localize: " + m;
-        return BA_E_INVALID;
-    }
+    const Stage stg{ctx, "ba_localize", ctx->stream};
+    if (const std::string m = loc_check(ctx, p, req, info); !m.empty()) return stg.invalid(m);
     const double t0 = now_ms();
     const size_t nc = (size_t)p->n_cams, np = (size_t)p->n_points, no = (size_t)p->n_obs;
     ba_loc_info full{};
@@ -71,23 +58,17 @@ extern "C" int32_t ba_localize(ba_context* ctx, ba_problem* p, const ba_loc_requ
 
     if (nwg) {
         HIPCHECK(ctx, hipSetDevice(ctx->device));
-        for (auto& e : ctx->loc_ev)
-            if (!e) HIPCHECK(ctx, hipEventCreate(&e));
-        hipStream_t s = ctx->stream;
-        auto nomem = [&](const char* what, size_t bytes) {
-            (void)hipGetLastError();
-            ctx->err = std::string("ba_localize: cannot allocate ") + what + " (" + std::to_string(bytes) + " bytes)";
-            return (int32_t)BA_E_NOMEM;
-        };
+        HIPCHECK(ctx, stg.events(ctx->loc_ev, 2));
+        hipStream_t s = stg.s;
         // in: cams (7 nc) | pts (3 np) | K (4) | uv (2 no) | depth (no) doubles, then obs_pt (no) ints
         // idx: the workgroups' records (LocCam), then the grouped indices
         // out: stats (8 nwg) | log (8 log_max) doubles
         const size_t in_d = 7 * nc + 3 * np + 4 + 3 * no;
         const size_t in_bytes = 8 * (in_d + 1) + 4 * no, idx_bytes = sizeof(LocCam) * nwg + 4 * (size_t)n_kept;
         const size_t out_bytes = 8 * (LOC_STAT * nwg + (size_t)LOG_W * (size_t)log_max);
-        if (ctx->buf[B_LOC_IN].ensure(in_bytes) != hipSuccess) return nomem("the window's copy", in_bytes);
-        if (ctx->buf[B_LOC_IDX].ensure(idx_bytes) != hipSuccess) return nomem("the grouped observations", idx_bytes);
-        if (ctx->buf[B_LOC_OUT].ensure(out_bytes) != hipSuccess) return nomem("the statistics", out_bytes);
+        if (int32_t rc = stg.ensure(B_LOC_IN, in_bytes, "the window's copy")) return rc;
+        if (int32_t rc = stg.ensure(B_LOC_IDX, idx_bytes, "the grouped observations")) return rc;
+        if (int32_t rc = stg.ensure(B_LOC_OUT, out_bytes, "the statistics")) return rc;
         double* d_cams = ctx->buf[B_LOC_IN].as<double>();
         double* d_pts = d_cams + 7 * nc;
         double* d_K = d_pts + 3 * np;
@@ -99,20 +80,14 @@ extern "C" int32_t ba_localize(ba_context* ctx, ba_problem* p, const ba_loc_requ
         int* d_idx = reinterpret_cast<int*>(d_wg + nwg);
         double* d_stats = ctx->buf[B_LOC_OUT].as<double>();
         double* d_log = d_stats + LOC_STAT * nwg;
-        auto h2d = [&](void* dst, const void* src, size_t bytes) {
-            return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-        };
-        auto d2h = [&](void* dst, const void* src, size_t bytes) {
-            return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-        };
-        HIPCHECK(ctx, h2d(d_cams, p->cams, 56 * nc));
-        HIPCHECK(ctx, h2d(d_pts, p->points, 24 * np));
-        HIPCHECK(ctx, h2d(d_K, p->intr, 32));
-        HIPCHECK(ctx, h2d(d_uv, p->obs_uv, 16 * no));
-        HIPCHECK(ctx, h2d(d_dep, p->obs_depth, 8 * no));
-        HIPCHECK(ctx, h2d(d_pt, p->obs_pt, 4 * no));
-        HIPCHECK(ctx, h2d(d_wg, wg.data(), sizeof(LocCam) * nwg));
-        HIPCHECK(ctx, h2d(d_idx, idx.data(), 4 * (size_t)n_kept));
+        HIPCHECK(ctx, stg.h2d(d_cams, p->cams, 56 * nc));
+        HIPCHECK(ctx, stg.h2d(d_pts, p->points, 24 * np));
+        HIPCHECK(ctx, stg.h2d(d_K, p->intr, 32));
+        HIPCHECK(ctx, stg.h2d(d_uv, p->obs_uv, 16 * no));
+        HIPCHECK(ctx, stg.h2d(d_dep, p->obs_depth, 8 * no));
+        HIPCHECK(ctx, stg.h2d(d_pt, p->obs_pt, 4 * no));
+        HIPCHECK(ctx, stg.h2d(d_wg, wg.data(), sizeof(LocCam) * nwg));
+        HIPCHECK(ctx, stg.h2d(d_idx, idx.data(), 4 * (size_t)n_kept));
         if (log_max) HIPCHECK(ctx, hipMemsetAsync(d_log, 0, 8 * (size_t)LOG_W * (size_t)log_max, s));
 
         LocArgs a{};
@@ -136,9 +111,9 @@ extern "C" int32_t ba_localize(ba_context* ctx, ba_problem* p, const ba_loc_requ
         // the solved poses come back through a copy: only the workgroups' cameras are written into prob
         std::vector<double> cams(7 * nc);
         std::vector<double> log((size_t)LOG_W * (size_t)log_max);
-        HIPCHECK(ctx, d2h(cams.data(), d_cams, 56 * nc));
-        HIPCHECK(ctx, d2h(stats.data(), d_stats, 8 * LOC_STAT * nwg));
-        HIPCHECK(ctx, d2h(log.data(), d_log, 8 * log.size()));
+        HIPCHECK(ctx, stg.d2h(cams.data(), d_cams, 56 * nc));
+        HIPCHECK(ctx, stg.d2h(stats.data(), d_stats, 8 * LOC_STAT * nwg));
+        HIPCHECK(ctx, stg.d2h(log.data(), d_log, 8 * log.size()));
         HIPCHECK(ctx, hipStreamSynchronize(s));
         (void)hipEventElapsedTime(&lm_ms, ctx->loc_ev[0], ctx->loc_ev[1]);
         for (size_t g = 0; g < nwg; ++g)
@@ -170,9 +145,7 @@ extern "C" int32_t ba_localize(ba_context* ctx, ba_problem* p, const ba_loc_requ
     }
     full.time_lm_ms = lm_ms;
     full.time_total_ms = now_ms() - t0;
-    const int32_t keep = info->struct_size;
-    std::memcpy(info, &full, std::min<size_t>((size_t)keep, sizeof(full)));
-    info->struct_size = keep;
+    sized_copy_out(info, full);
     ctx->err.clear();
     return BA_OK;
 }

@@ -4,54 +4,36 @@
 // ba_local_window is a stage beside the LM loop, like ba_covisibility, whose observation and bit-matrix buffers it
 // shares: nothing the plan or the LM loop reads is written. ba_solve_local is ba_solve on a shadow problem the
 // context keeps.
-#include "ba_context.h"
 #include "ba_covis.h"
 #include "ba_local.h"
+#include "ba_stage.h"
 
 using namespace miba;
 
 namespace {
 
-const char* local_validate(const ba_problem* p) {
-    if (p->n_cams < 0 || p->n_points < 0 || p->n_obs < 0) return "invalid problem sizes";
-    if (p->n_obs && (!p->obs_cam || !p->obs_pt || !p->obs_depth)) return "null problem buffer";
-    for (int32_t k = 0; k < p->n_obs; ++k)
-        if (p->obs_cam[k] < 0 || p->obs_cam[k] >= p->n_cams || p->obs_pt[k] < 0 || p->obs_pt[k] >= p->n_points)
-            return "observation index out of range";
-    return "";
-}
-
 // The selection into ctx->local (every list sized to what it holds) and `full`; the request's buffers are the caller's.
+// (Its allocation failures read "ba_local_window: ..." under either entry point.)
 int32_t local_select(ba_context* ctx, const ba_problem* p, int center, int min_weight, int max_local, ba_local_info& full) {
     const double t0 = now_ms();
+    const Stage stg{ctx, "ba_local_window", ctx->stream};
     HIPCHECK(ctx, hipSetDevice(ctx->device));
-    for (auto& e : ctx->local_ev)
-        if (!e) HIPCHECK(ctx, hipEventCreate(&e));
-    hipStream_t s = ctx->stream;
+    HIPCHECK(ctx, stg.events(ctx->local_ev, 2));
+    hipStream_t s = stg.s;
     hipEvent_t* ev = ctx->local_ev;
     const size_t nc = (size_t)p->n_cams, np = (size_t)p->n_points, no = (size_t)p->n_obs;
     const size_t nw = covis_row_words(p->n_points);
     ba_context::Local& out = ctx->local;
     if (min_weight <= 0) min_weight = 1;
 
-    auto nomem = [&](const char* what, size_t bytes) {
-        (void)hipGetLastError();
-        ctx->err = std::string("ba_local_window: cannot allocate ") + what + " (" + std::to_string(bytes) + " bytes)";
-        return (int32_t)BA_E_NOMEM;
-    };
     // work: P (nw words) | wcnt, wrank (nw) | cnt, sel, cam_new (nc) | pt_new (np) | oscan (no) | the scans' workgroup
     // sums | the two totals; out: pt_index (np) | obs_index, sub_cam, sub_pt (no)
     const size_t nbs = (size_t)std::max(local_scan_blocks(nw), local_scan_blocks(no)) + 1;
-    const size_t obs_bytes = 16 * std::max<size_t>(no, 1), bits_bytes = 8 * std::max<size_t>(nc * nw, 1);
     const size_t work_bytes = 8 * nw + 4 * (2 * nw + 3 * nc + np + no + nbs + 2), out_bytes = 4 * (np + 3 * no + 1);
-    if (ctx->buf[B_COVIS_OBS].ensure(obs_bytes) != hipSuccess) return nomem("the observation copies", obs_bytes);
-    if (ctx->buf[B_COVIS_BITS].ensure(bits_bytes) != hipSuccess) return nomem("the camera x point bit matrix", bits_bytes);
-    if (ctx->buf[B_LOCAL_WORK].ensure(work_bytes) != hipSuccess) return nomem("the selection scratch", work_bytes);
-    if (ctx->buf[B_LOCAL_OUT].ensure(out_bytes) != hipSuccess) return nomem("the selection outputs", out_bytes);
-    double* d_dep = ctx->buf[B_COVIS_OBS].as<double>();
-    int* d_cam = reinterpret_cast<int*>(d_dep + no);
-    int* d_pt = d_cam + no;
-    unsigned long long* d_bits = ctx->buf[B_COVIS_BITS].as<unsigned long long>();
+    if (int32_t rc = stg.ensure(B_COVIS_OBS, covis_obs_bytes(no), "the observation copies")) return rc;
+    if (int32_t rc = stg.ensure(B_COVIS_BITS, covis_bits_bytes(nc, nw), "the camera x point bit matrix")) return rc;
+    if (int32_t rc = stg.ensure(B_LOCAL_WORK, work_bytes, "the selection scratch")) return rc;
+    if (int32_t rc = stg.ensure(B_LOCAL_OUT, out_bytes, "the selection outputs")) return rc;
     unsigned long long* d_P = ctx->buf[B_LOCAL_WORK].as<unsigned long long>();
     int* d_wcnt = reinterpret_cast<int*>(d_P + nw);
     int* d_wrank = d_wcnt + nw;
@@ -67,24 +49,14 @@ int32_t local_select(ba_context* ctx, const ba_problem* p, int center, int min_w
     int* d_sub_cam = d_obs_index + no;
     int* d_sub_pt = d_sub_cam + no;
 
-    auto h2d = [&](void* dst, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    auto d2h = [&](void* dst, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
     float ms = 0.f, part = 0.f;
     // 1. the bit matrix and the weight row
-    HIPCHECK(ctx, h2d(d_dep, p->obs_depth, sizeof(double) * no));
-    HIPCHECK(ctx, h2d(d_cam, p->obs_cam, sizeof(int32_t) * no));
-    HIPCHECK(ctx, h2d(d_pt, p->obs_pt, sizeof(int32_t) * no));
-    HIPCHECK(ctx, hipEventRecord(ev[0], s));
-    HIPCHECK(ctx, hipMemsetAsync(d_bits, 0, bits_bytes, s));
-    HIPCHECK(ctx, launch_covis_bits(d_cam, d_pt, d_dep, p->n_obs, p->n_points, d_bits, s));
-    HIPCHECK(ctx, launch_local_rows(d_bits, d_bits + (size_t)center * nw, p->n_cams, nw, d_cnt, s));
+    CovisBits cb{};
+    if (int32_t rc = covis_upload_bits(stg, p, ev[0], cb)) return rc;
+    HIPCHECK(ctx, launch_local_rows(cb.bits, cb.bits + (size_t)center * nw, p->n_cams, nw, d_cnt, s));
     HIPCHECK(ctx, hipEventRecord(ev[1], s));
     out.w.assign(nc, 0);
-    HIPCHECK(ctx, d2h(out.w.data(), d_cnt, sizeof(int32_t) * nc));
+    HIPCHECK(ctx, stg.d2h(out.w.data(), d_cnt, sizeof(int32_t) * nc));
     HIPCHECK(ctx, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&part, ev[0], ev[1]);
     ms += part;
@@ -122,12 +94,12 @@ int32_t local_select(ba_context* ctx, const ba_problem* p, int center, int min_w
 
     // 3. the local points and the cameras that see them
     std::vector<int32_t> cnt(nc, 0);
-    HIPCHECK(ctx, h2d(d_sel, L.data(), sizeof(int32_t) * L.size()));
+    HIPCHECK(ctx, stg.h2d(d_sel, L.data(), sizeof(int32_t) * L.size()));
     HIPCHECK(ctx, hipEventRecord(ev[0], s));
-    HIPCHECK(ctx, launch_local_or(d_bits, d_sel, (int)L.size(), nw, d_P, d_wcnt, s));
-    HIPCHECK(ctx, launch_local_rows(d_bits, d_P, p->n_cams, nw, d_cnt, s));
+    HIPCHECK(ctx, launch_local_or(cb.bits, d_sel, (int)L.size(), nw, d_P, d_wcnt, s));
+    HIPCHECK(ctx, launch_local_rows(cb.bits, d_P, p->n_cams, nw, d_cnt, s));
     HIPCHECK(ctx, hipEventRecord(ev[1], s));
-    HIPCHECK(ctx, d2h(cnt.data(), d_cnt, sizeof(int32_t) * nc));
+    HIPCHECK(ctx, stg.d2h(cnt.data(), d_cnt, sizeof(int32_t) * nc));
     HIPCHECK(ctx, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&part, ev[0], ev[1]);
     ms += part;
@@ -148,13 +120,13 @@ int32_t local_select(ba_context* ctx, const ba_problem* p, int center, int min_w
 
     // 4. the points' ranks and the observations' compaction
     int32_t total[2] = {0, 0};
-    HIPCHECK(ctx, h2d(d_cam_new, cam_new.data(), sizeof(int32_t) * nc));
+    HIPCHECK(ctx, stg.h2d(d_cam_new, cam_new.data(), sizeof(int32_t) * nc));
     HIPCHECK(ctx, hipEventRecord(ev[0], s));
     HIPCHECK(ctx, launch_local_points(d_P, d_wcnt, p->n_points, nw, d_wrank, d_bsum, d_pt_new, d_pt_index, d_total, s));
-    HIPCHECK(ctx, launch_local_obs(d_cam, d_pt, d_dep, p->n_obs, d_P, d_cam_new, d_pt_new, d_oscan, d_bsum, d_obs_index,
+    HIPCHECK(ctx, launch_local_obs(cb.cam, cb.pt, cb.dep, p->n_obs, d_P, d_cam_new, d_pt_new, d_oscan, d_bsum, d_obs_index,
                                    d_sub_cam, d_sub_pt, d_total + 1, s));
     HIPCHECK(ctx, hipEventRecord(ev[1], s));
-    HIPCHECK(ctx, d2h(total, d_total, sizeof(total)));
+    HIPCHECK(ctx, stg.d2h(total, d_total, sizeof(total)));
     HIPCHECK(ctx, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&part, ev[0], ev[1]);
     ms += part;
@@ -166,10 +138,10 @@ int32_t local_select(ba_context* ctx, const ba_problem* p, int center, int min_w
     out.obs_index.resize((size_t)total[1]);
     out.obs_cam.resize((size_t)total[1]);
     out.obs_pt.resize((size_t)total[1]);
-    HIPCHECK(ctx, d2h(out.pt_index.data(), d_pt_index, sizeof(int32_t) * total[0]));
-    HIPCHECK(ctx, d2h(out.obs_index.data(), d_obs_index, sizeof(int32_t) * total[1]));
-    HIPCHECK(ctx, d2h(out.obs_cam.data(), d_sub_cam, sizeof(int32_t) * total[1]));
-    HIPCHECK(ctx, d2h(out.obs_pt.data(), d_sub_pt, sizeof(int32_t) * total[1]));
+    HIPCHECK(ctx, stg.d2h(out.pt_index.data(), d_pt_index, sizeof(int32_t) * total[0]));
+    HIPCHECK(ctx, stg.d2h(out.obs_index.data(), d_obs_index, sizeof(int32_t) * total[1]));
+    HIPCHECK(ctx, stg.d2h(out.obs_cam.data(), d_sub_cam, sizeof(int32_t) * total[1]));
+    HIPCHECK(ctx, stg.d2h(out.obs_pt.data(), d_sub_pt, sizeof(int32_t) * total[1]));
     HIPCHECK(ctx, hipStreamSynchronize(s));
     full.n_points = total[0];
     full.n_obs = total[1];
@@ -180,13 +152,8 @@ int32_t local_select(ba_context* ctx, const ba_problem* p, int center, int min_w
 
 // the arguments' verdict shared by the two entry points ("" when they are usable)
 std::string local_check(ba_context* ctx, const ba_problem* p, const ba_local_request* req, const ba_local_info* info) {
-    if (!p || !req || !info) return "null argument";
-    if (req->struct_size < BA_LOCAL_REQUEST_MIN_SIZE)
-        return "request struct_size below BA_LOCAL_REQUEST_MIN_SIZE (set it with BA_LOCAL_REQUEST_INIT)";
-    if (info->struct_size < BA_LOCAL_INFO_MIN_SIZE)
-        return "info struct_size below BA_LOCAL_INFO_MIN_SIZE (set it with BA_LOCAL_INFO_INIT)";
-    if (ctx->W.comm.on() || ctx->comm_parked.on()) return "contexts with landmark shards (ba_comm_init*) are not supported";
-    if (const char* m = local_validate(p); *m) return m;
+    if (const std::string m = stage_refusal(ctx, p, req, info, STAGE_SIZES(BA_LOCAL)); !m.empty()) return m;
+    if (const char* m = stage_validate_problem(p, STAGE_OBS); *m) return m;
     if (req->center < 0 || req->center >= p->n_cams)
         return "center = " + std::to_string(req->center) + " is out of range (" + std::to_string(p->n_cams) + " cameras)";
     return "";
@@ -206,9 +173,7 @@ void local_publish(const ba_context* ctx, const ba_local_request* req, const ba_
     put(req->sub_obs_cam, o.obs_cam);
     put(req->sub_obs_pt, o.obs_pt);
     put(req->cam_local, o.is_local);
-    const int32_t keep = info->struct_size;
-    std::memcpy(info, &full, std::min<size_t>((size_t)keep, sizeof(full)));
-    info->struct_size = keep;
+    sized_copy_out(info, full);
 }
 
 }  // namespace
@@ -216,10 +181,8 @@ void local_publish(const ba_context* ctx, const ba_local_request* req, const ba_
 extern "C" int32_t ba_local_window(ba_context* ctx, const ba_problem* p, const ba_local_request* req,
                                    ba_local_info* info) {
     if (!ctx) { miba_set_error("null context"); return BA_E_INVALID; }
-    if (const std::string m = local_check(ctx, p, req, info); !m.empty()) {
-        ctx->err = "ba_local_window: " + m;
-        return BA_E_INVALID;
-    }
+    if (const std::string m = local_check(ctx, p, req, info); !m.empty())
+        return Stage{ctx, "ba_local_window", ctx->stream}.invalid(m);
     ba_local_info full{};
     if (int32_t rc = local_select(ctx, p, req->center, req->min_weight, req->max_local, full)) return rc;
     local_publish(ctx, req, full, info);
@@ -230,12 +193,11 @@ extern "C" int32_t ba_local_window(ba_context* ctx, const ba_problem* p, const b
 extern "C" int32_t ba_solve_local(ba_context* ctx, ba_problem* p, const ba_local_request* req, ba_local_info* info,
                                   ba_summary* sum) {
     if (!ctx) { miba_set_error("null context"); return BA_E_INVALID; }
-    auto invalid = [&](const std::string& m) { ctx->err = "ba_solve_local: " + m; return (int32_t)BA_E_INVALID; };
-    if (!sum) return invalid("null argument");
-    if (const std::string m = local_check(ctx, p, req, info); !m.empty()) return invalid(m);
-    if ((p->n_cams && !p->cams) || (p->n_points && !p->points) || !p->intr || !p->intr_prior ||
-        (p->n_obs && !p->obs_uv))
-        return invalid("null problem buffer");
+    const Stage stg{ctx, "ba_solve_local", ctx->stream};
+    if (!sum) return stg.invalid("null argument");
+    if (const std::string m = local_check(ctx, p, req, info); !m.empty()) return stg.invalid(m);
+    // (the solve's own buffers come after the selection's checks, the center's included)
+    if (stage_missing_buffer(p, STAGE_PARAMS)) return stg.invalid(kNullBuffer);
     ba_local_info full{};
     if (int32_t rc = local_select(ctx, p, req->center, req->min_weight, req->max_local, full)) return rc;
     local_publish(ctx, req, full, info);

@@ -9,13 +9,13 @@
 // over the workgroups' sums with a carry, the offsets added by the consumer): no workgroup waits for another inside
 // a launch.
 #include "ba_local.h"
+#include "ba_obs.h"
 #include "ba_scan.h"
 
 namespace miba {
 
 static_assert(LOCAL_TPB == SCAN_TPB, "block_excl (ba_scan.h) scans one workgroup of LOCAL_TPB threads");
 
-__device__ __forceinline__ bool local_admissible(double depth) { return depth > 1e-15; }
 __device__ __forceinline__ bool local_has(const unsigned long long* __restrict__ P, unsigned pt) {
     return (P[pt >> 6] >> (pt & 63u)) & 1ull;
 }
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(LOCAL_TPB) void k_local_scan_keep(const int* __rest
                                                                int* __restrict__ out, int* __restrict__ bsum) {
     __shared__ int sh[LOCAL_TPB / 64];
     const size_t k = (size_t)blockIdx.x * LOCAL_TPB + threadIdx.x;
-    const int v = (k < n && local_admissible(obs_depth[k]) && local_has(P, (unsigned)obs_pt[k])) ? 1 : 0;
+    const int v = (k < n && obs_admissible(obs_depth[k]) && local_has(P, (unsigned)obs_pt[k])) ? 1 : 0;
     int tot;
     const int e = block_excl(v, sh, tot);
     if (k < n) out[k] = e;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(LOCAL_TPB) void k_local_scatter(const int* __restri
                                                              int* __restrict__ obs_index, int* __restrict__ sub_cam,
                                                              int* __restrict__ sub_pt) {
     const size_t k = (size_t)blockIdx.x * LOCAL_TPB + threadIdx.x;
-    if (k >= n || !local_admissible(obs_depth[k])) return;
+    if (k >= n || !obs_admissible(obs_depth[k])) return;
     const int pt = obs_pt[k];
     if (!local_has(P, (unsigned)pt)) return;
     const int pos = bsum[blockIdx.x] + oscan[k];

@@ -4,29 +4,22 @@
 // Nothing the LM loop reads is written: the report has buffers of its own and never touches the LM state.
 #include <cmath>
 
-#include "ba_context.h"
 #include "ba_resid.h"
+#include "ba_stage.h"
 
 using namespace miba;
 
 extern "C" int32_t ba_residuals(ba_context* ctx, const ba_problem* p, const ba_res_request* req, ba_res_info* info) {
     if (!ctx) { miba_set_error("null context"); return BA_E_INVALID; }
-    auto invalid = [&](const std::string& m) { ctx->err = "ba_residuals: " + m; return (int32_t)BA_E_INVALID; };
-    if (!p || !req || !info) return invalid("null argument");
-    if (req->struct_size < BA_RES_REQUEST_MIN_SIZE)
-        return invalid("request struct_size below BA_RES_REQUEST_MIN_SIZE (set it with BA_RES_REQUEST_INIT)");
-    if (info->struct_size < BA_RES_INFO_MIN_SIZE)
-        return invalid("info struct_size below BA_RES_INFO_MIN_SIZE (set it with BA_RES_INFO_INIT)");
-    if (ctx->W.comm.on() || ctx->comm_parked.on())
-        return invalid("contexts with landmark shards (ba_comm_init*) are not supported");
+    const Stage stg{ctx, "ba_residuals", ctx->stream};
+    if (const std::string m = stage_refusal(ctx, p, req, info, STAGE_SIZES(BA_RES)); !m.empty()) return stg.invalid(m);
     const double t0 = now_ms();
     HIPCHECK(ctx, hipSetDevice(ctx->device));
     if (int rc = prepare(ctx, p)) return rc;
     ctx->err.clear();
-    for (auto& e : ctx->res_ev)
-        if (!e) HIPCHECK(ctx, hipEventCreate(&e));
+    HIPCHECK(ctx, stg.events(ctx->res_ev, 2));
     const DevProblem& P = ctx->P;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = stg.s;
     const size_t no = (size_t)p->n_obs, np = (size_t)p->n_points, nc = (size_t)p->n_cams;
     const size_t na = (size_t)P.n_adm, nseg = (size_t)P.n_seg;
     const bool want_flags = req->obs_flags || req->obs_depth_culled;
@@ -40,6 +33,7 @@ extern "C" int32_t ba_residuals(ba_context* ctx, const ba_problem* p, const ba_r
     t.depth_on = (req->max_depth_abs > 0 || req->max_depth_rel > 0) ? 1 : 0;
 
     // slot-order values | caller-order values | statistics (each part 8-byte aligned: doubles first)
+    // (a failed allocation is BA_E_DEVICE with the HIP text here and in ba_covariance, not Stage::ensure's BA_E_NOMEM)
     HIPCHECK(ctx, ctx->buf[B_RES_PO].ensure(44 * std::max<size_t>(na, 1)));
     if (per_obs) HIPCHECK(ctx, ctx->buf[B_RES_OBS].ensure(44 * std::max<size_t>(no, 1)));
     const size_t n_stat = BA_RES_STAT_N * np + RES_PART_N * nseg + BA_RES_STAT_N * nc + RES_TOTALS_N;
@@ -67,15 +61,12 @@ extern "C" int32_t ba_residuals(ba_context* ctx, const ba_problem* p, const ba_r
     std::vector<int32_t> flags_tmp;
     int32_t* flags_out = req->obs_flags;
     if (want_flags && !flags_out && no) { flags_tmp.resize(no); flags_out = flags_tmp.data(); }
-    auto d2h = [&](void* dst, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    HIPCHECK(ctx, d2h(tot, b.totals, sizeof(tot)));
-    if (req->obs_err) HIPCHECK(ctx, d2h(req->obs_err, b.obs_err, sizeof(double) * 4 * no));
-    if (req->obs_cost) HIPCHECK(ctx, d2h(req->obs_cost, b.obs_cost, sizeof(double) * no));
-    if (flags_out) HIPCHECK(ctx, d2h(flags_out, b.obs_flags, sizeof(int32_t) * no));
-    if (req->cam_stats) HIPCHECK(ctx, d2h(req->cam_stats, b.cam_stats, sizeof(double) * BA_RES_STAT_N * nc));
-    if (req->point_stats) HIPCHECK(ctx, d2h(req->point_stats, b.point_stats, sizeof(double) * BA_RES_STAT_N * np));
+    HIPCHECK(ctx, stg.d2h(tot, b.totals, sizeof(tot)));
+    if (req->obs_err) HIPCHECK(ctx, stg.d2h(req->obs_err, b.obs_err, sizeof(double) * 4 * no));
+    if (req->obs_cost) HIPCHECK(ctx, stg.d2h(req->obs_cost, b.obs_cost, sizeof(double) * no));
+    if (flags_out) HIPCHECK(ctx, stg.d2h(flags_out, b.obs_flags, sizeof(int32_t) * no));
+    if (req->cam_stats) HIPCHECK(ctx, stg.d2h(req->cam_stats, b.cam_stats, sizeof(double) * BA_RES_STAT_N * nc));
+    if (req->point_stats) HIPCHECK(ctx, stg.d2h(req->point_stats, b.point_stats, sizeof(double) * BA_RES_STAT_N * np));
     HIPCHECK(ctx, hipStreamSynchronize(s));
     if (req->obs_depth_culled)
         for (size_t k = 0; k < no; ++k)
@@ -101,8 +92,6 @@ extern "C" int32_t ba_residuals(ba_context* ctx, const ba_problem* p, const ba_r
     (void)hipEventElapsedTime(&ms, ctx->res_ev[0], ctx->res_ev[1]);
     full.time_eval_ms = ms;
     full.time_total_ms = now_ms() - t0;
-    const int32_t keep = info->struct_size;
-    std::memcpy(info, &full, std::min<size_t>((size_t)keep, sizeof(full)));
-    info->struct_size = keep;
+    sized_copy_out(info, full);
     return BA_OK;
 }
