@@ -104,6 +104,9 @@ enum BufId {
     // ba_localize (allocated on its first call): its own copy of the window (poses, points, intrinsics, observation
     // values), the grouped observation indices with the workgroups' records, and the statistics and log it writes
     B_LOC_IN, B_LOC_IDX, B_LOC_OUT,
+    // ba_refine_points (allocated on its first call): its own copy of the window, the observation indices grouped by
+    // point with the points' records, and the statistics, solved positions and log it writes
+    B_PTS_IN, B_PTS_IDX, B_PTS_OUT,
     B_COUNT
 };
 
@@ -191,6 +194,7 @@ struct ba_context {
     } local;
     hipEvent_t local_ev[2] = {nullptr, nullptr};  // ba_local_window's events around its kernels (first call)
     hipEvent_t loc_ev[2] = {nullptr, nullptr};    // ba_localize's events around its kernel (first call)
+    hipEvent_t pts_ev[2] = {nullptr, nullptr};    // ba_refine_points' events around its kernel (first call)
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
     int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout

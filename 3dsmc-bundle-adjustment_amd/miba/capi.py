@@ -427,6 +427,53 @@ class BaLocInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+PTS_STAT_N = 8  # BA_PTS_STAT_N (the fields of LOC_STAT_FIELDS, per point)
+
+
+class BaPtsRequest(C.Structure):
+    """Mirror of ``ba_pts_request`` (ba_refine_points). ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("min_obs", C.c_int32),
+        ("pt_mask", _u8p),
+        ("pt_stats", _dp),
+        ("log_pt", C.c_int32),
+        ("log_max_rows", C.c_int32),
+        ("log_rows", _dp),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaPtsInfo(C.Structure):
+    """Mirror of ``ba_pts_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_selected", C.c_int32),
+        ("n_solved", C.c_int32),
+        ("n_convergence", C.c_int32),
+        ("n_no_convergence", C.c_int32),
+        ("n_failure", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("log_rows", C.c_int32),
+        ("time_lm_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

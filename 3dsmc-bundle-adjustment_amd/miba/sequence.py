@@ -86,14 +86,16 @@ def make_tum_sequence(n_keyframes: int = 36, n_landmarks: int = 1500, seed: int 
 
 def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_frequency: int = 10,
                  window_size: int = 10, order=None, solve_local=None, min_weight: int = 15, max_local: int = 0,
-                 localize=None):
+                 localize=None, refine_points=None):
     """main.cpp:150-195 with one keyframe per frame. Returns (trajectory_text, summaries, intr_opt);
     ``keyframes`` / ``landmarks`` are updated in place. ``order`` (opt-in, default off) goes to
     window.window_optimize: ``"auto"`` solves every window in its co-visibility order. ``solve_local`` (opt-in,
     default off; a ``Solver().solve_local``): whenever the schedule fires, window.local_optimize centred on the
     newest keyframe of the window (``min_weight``, ``max_local``) in place of the last-k window. ``localize`` (opt-in,
     default off; a ``Solver().localize``): every keyframe's pose is refined against the map as it stands when the
-    keyframe is appended (window.localize_keyframe), before the schedule looks at it."""
+    keyframe is appended (window.localize_keyframe), before the schedule looks at it. ``refine_points`` (opt-in,
+    default off; a ``Solver().refine_points``): right after that, the landmarks the new keyframe re-observes are
+    refined against the keyframes as they stand (window.refine_landmarks)."""
     intr_opt = np.array(intr_init, dtype=np.float64)
     summaries = []
     pending = list(keyframes)
@@ -107,6 +109,8 @@ def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_fre
             if localize is not None:
                 window.localize_keyframe(len(keyframes) - 1, keyframes, landmarks, intr_opt, localize, seen)
                 seen.update(keyframes[-1].global_points_map.values())
+            if refine_points is not None:
+                window.refine_landmarks(len(keyframes) - 1, keyframes, landmarks, intr_opt, refine_points)
         run, a, b, fin = window.window_schedule(frame_frequency, window_size, len(keyframes), not tracked,
                                                 finished, tracked)
         if run and solve_local is not None:

@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib
 from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaCovisInfo,
                    BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest, BaLocInfo, BaLocRequest, LOC_STAT_N,
+                   BaPtsInfo, BaPtsRequest, PTS_STAT_N,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -204,6 +205,42 @@ class Solver:
         self._check(self._L.ba_localize(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_localize")
         out = info.as_dict()
         out["stats"] = stats[:nc]
+        out["log"] = None if log is None else log[: min(info.log_rows, log.shape[0])].copy()
+        return out
+
+    def refine_points(self, prob: ProblemArrays, points=None, log_pt=None, min_obs: int = 1) -> dict:
+        """ba_refine_points: refine the positions of the points ``points`` (indices or a boolean mask of n_points
+        entries; ``None``: every point) against the cameras and intrinsics of ``prob`` as they stand, each point on its
+        own observations alone; a point with fewer than ``min_obs`` admissible observations is left as it is.
+        ``prob.points`` is updated in place; nothing else in ``prob`` changes and the context's plan and LM state are
+        not touched. Returns the fields of ``ba_pts_info``, ``stats`` (n_points, 8) (see ``capi.LOC_STAT_FIELDS``; a
+        point that was not selected or has too few admissible observations has stats[6] = -1) and ``log``: point
+        ``log_pt``'s iteration rows (``iteration_log``'s layout), ``None`` without ``log_pt``."""
+        req, info = BaPtsRequest(), BaPtsInfo()
+        npt = prob.n_points
+        req.min_obs = int(min_obs)
+        if points is not None:
+            c = np.asarray(points)
+            if c.dtype == bool:
+                if c.shape != (npt,):
+                    raise ValueError("a boolean point mask must have one entry per point")
+                mask = np.ascontiguousarray(c, dtype=np.uint8)
+            else:
+                mask = np.zeros(npt, dtype=np.uint8)
+                mask[np.asarray(c, dtype=np.int64).reshape(-1)] = 1
+            if npt:
+                req.pt_mask = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        stats = np.zeros((max(npt, 1), PTS_STAT_N))
+        req.pt_stats = _dptr(stats)
+        req.log_pt = -1
+        log = None
+        if log_pt is not None:
+            log = np.zeros((max(int(self.options.max_num_iterations), 0) + 1, _lib.LOG_WIDTH))
+            req.log_pt, req.log_max_rows, req.log_rows = int(log_pt), log.shape[0], _dptr(log)
+        ps = prob.struct()
+        self._check(self._L.ba_refine_points(self._h, C.byref(ps), C.byref(req), C.byref(info)), "ba_refine_points")
+        out = info.as_dict()
+        out["stats"] = stats[:npt]
         out["log"] = None if log is None else log[: min(info.log_rows, log.shape[0])].copy()
         return out
 

@@ -168,6 +168,57 @@ def localize_keyframe(k: int, keyframes: list, landmarks: dict, intr, localize, 
     return out
 
 
+def refine_frame(k: int, keyframes: list, landmarks: dict, intr):
+    """The landmarks keyframe ``k`` brings new evidence about, as ``ProblemArrays`` for a structure-only refinement
+    (``None`` when nothing qualifies): the landmarks ``k`` observes that an earlier keyframe (index < k) also observes,
+    in the order of k's global_points_map, with all their admissible observations in keyframes 0 .. k (keyframe by
+    keyframe, each in the order of its global_points_map). The cameras are those k + 1 keyframes, constant to the
+    refinement. ``meta['landmark_ids']`` names the landmark of every point."""
+    kf = keyframes[k]
+    earlier = set()
+    for other in keyframes[:k]:
+        earlier.update(other.global_points_map.values())
+    pt_index, ids = {}, []
+    for landmark_id in kf.global_points_map.values():
+        if landmark_id in earlier and landmark_id not in pt_index:
+            pt_index[landmark_id] = len(ids)
+            ids.append(landmark_id)
+    if not ids:
+        return None
+    obs_cam, obs_pt, uv, depth = [], [], [], []
+    for n in range(k + 1):
+        other = keyframes[n]
+        for local_id, landmark_id in other.global_points_map.items():
+            d = float(other.points3d_local[local_id][2])
+            if d <= 1e-15 or landmark_id not in pt_index:
+                continue
+            obs_cam.append(n)
+            obs_pt.append(pt_index[landmark_id])
+            uv.append((float(other.keypoints[local_id][0]), float(other.keypoints[local_id][1])))
+            depth.append(d)
+    K = np.array(intr, dtype=np.float64)
+    cams = np.array([np.array(o.T_w_c, dtype=np.float64) for o in keyframes[:k + 1]]).reshape(-1, 7)
+    pts = np.array([np.array(landmarks[lid], dtype=np.float64) for lid in ids]).reshape(-1, 3)
+    return ProblemArrays(cams, pts, K, K.copy(), np.array(obs_cam, dtype=np.int32), np.array(obs_pt, dtype=np.int32),
+                         np.array(uv, dtype=np.float64).reshape(-1, 2), np.array(depth, dtype=np.float64), fixed_cam=-1,
+                         meta=dict(landmark_ids=ids))
+
+
+def refine_landmarks(k: int, keyframes: list, landmarks: dict, intr, refine_points):
+    """Structure-only refinement of the landmarks keyframe ``k`` re-observes, against the keyframes as they stand:
+    ``refine_frame`` handed to ``refine_points`` -- a ``miba.solver.Solver().refine_points`` -- and the solved landmarks
+    (stats[:, 6] >= 0) written back, and only those. Keyframes and intrinsics are constant. With no landmark shared
+    with an earlier keyframe it does nothing and returns ``None``."""
+    prob = refine_frame(k, keyframes, landmarks, intr)
+    if prob is None:
+        return None
+    out = refine_points(prob)
+    for q, lid in enumerate(prob.meta["landmark_ids"]):
+        if out["stats"][q][6] >= 0:
+            landmarks[lid] = prob.points[q].copy()
+    return out
+
+
 def window_schedule(frame_frequency: int, window_size: int, n_keyframes: int, tracking_finished: bool,
                     optimization_finished: bool, tracked_this_frame: bool):
     """(run, kf_i, kf_f, finishes) for main.cpp:163-183."""

@@ -57,7 +57,9 @@ extern "C" {
  *   2, additive  ba_set_constant_cameras (a set of constant poses beside fixed_cam), ba_local_window with
  *                ba_local_request / ba_local_info (both sized structs) and ba_solve_local; nothing else changed.
  *   2, additive  ba_localize with ba_loc_request / ba_loc_info (both sized structs): pose-only refinement of keyframes
- *                against a constant map; ba_options and everything else unchanged. */
+ *                against a constant map; ba_options and everything else unchanged.
+ *   2, additive  ba_refine_points with ba_pts_request / ba_pts_info (both sized structs): structure-only refinement of
+ *                landmarks against constant keyframes; ba_options and everything else unchanged. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -579,6 +581,71 @@ typedef struct ba_loc_info {
 #define BA_LOC_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 #define BA_LOC_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 int32_t ba_localize(ba_context* ctx, ba_problem* prob, const ba_loc_request* req, ba_loc_info* info);
+
+/* ---- point refinement: structure-only refinement against constant cameras ----
+ * The other block of the alternation whose first block is ba_localize, and the optimiser an SfM or SLAM back-end
+ * calls after triangulation or map-point insertion: every selected point's position is refined with the cameras and
+ * the intrinsics held constant. With those constant the points decouple, so a call is a batch of independent
+ * 3-parameter problems, one row of 16 lanes each (four points per wave), the whole trust-region loop inside one
+ * kernel launch. The contract is ba_localize's with cameras and points swapped.
+ * Cost. A point p is solved if it is selected and has at least min_obs (<= 0: 1) admissible observations (depth >
+ * 1e-15). For each such point the call minimises over X_p alone the cost ba_solve has on the one-point window made
+ * of p's observations with every camera constant: the sum over p's admissible observations of 0.5 rho_repr + 0.5
+ * rho_unpr with the weights 1 / N_p and weight_unpr / N_p, N_p being p's OWN admissible count, and the Huber
+ * parameters of the context's options. The IntrinsicsPrior block has only constant parameters and is not part of the
+ * cost.
+ * Loop. The LM loop of ba_solve restated for three Euclidean parameters, every option taken from the context's
+ * ba_options: Jacobi scaling 1 / (1 + sqrt(column norm^2)) taken at iteration 0; the LM diagonal clamp(diag,
+ * min_lm_diagonal, max_lm_diagonal) / radius; a 3x3 Cholesky with IEEE square root and division; the step delta =
+ * -scale * y applied as X + delta; the model cost change from the unscaled Jacobian; rho against
+ * min_relative_decrease; the radius update and the decrease factor; a non-positive or non-finite Cholesky pivot or a
+ * model cost change that is not positive is an invalid step, max_num_consecutive_invalid_steps of them end the point
+ * with BA_FAILURE; the gradient tolerance on max_i |X_i - (X_i + -g_i)|, the parameter tolerance with |X|_2 of the
+ * three coordinates, the function tolerance; max_num_iterations. log_rows receives point log_pt's rows in
+ * ba_iteration_log's layout (the gradient max-norm column is filled in every row).
+ * pt_stats, BA_PTS_STAT_N values per point of the window:
+ *   [0] admissible observations N_p   [1] initial cost            [2] final cost (the lowest cost of any iteration)
+ *   [3] LM iterations                 [4] successful steps (Ceres convention: includes iteration 0)
+ *   [5] unsuccessful steps            [6] termination type (BA_CONVERGENCE / BA_NO_CONVERGENCE / BA_FAILURE), or -1 for
+ *   a point that was not selected or has fewer than min_obs admissible observations   [7] the message kind of the LM
+ *   loop (the msg of ba_debug_step_state). A point with [6] = -1 has zeros elsewhere.
+ *   [2] follows ceres::Solver::Summary::final_cost: the lowest cost any iteration evaluated, a rejected candidate's
+ *   included, so it can lie below the cost at the returned position.
+ * Inputs. prob->fixed_cam and the context's constant set (ba_set_constant_cameras) are not consulted: every camera is
+ * constant here, and pt_mask alone says which points are refined.
+ * Outputs. Solved points are updated in place; cameras, intrinsics, the observation arrays, the unselected points and
+ * the selected points below min_obs stay bitwise untouched. A point whose evaluation at the given position is not
+ * finite ends with BA_FAILURE (the evaluation-failed message), keeps its position and writes no log row.
+ * Stand-alone like ba_localize: validates the window as ba_prepare does, works on device buffers of its own (the
+ * context keeps them between calls; every call uploads the window) and touches neither the context's plan nor its LM
+ * state nor the plan cache: a ba_solve_prepared after it is bitwise the solve without it.
+ * Reproducibility. No floating-point atomics; every sum has one fixed order, set by the observation's position among
+ * its point's admissible observations in the caller's order, and a point's result does not depend on what else is in
+ * the call: alone or among 10^5 others it gives the same bits.
+ * ba_pts_info: n_selected points the mask names, n_solved of them with min_obs admissible observations (the grid's
+ * rows), n_convergence + n_no_convergence + n_failure = n_solved, max_iterations the most LM iterations any point
+ * took, log_rows the rows point log_pt's loop produced (iterations + 1, of which the first min(log_rows,
+ * log_max_rows) are written and the rest of the buffer is left alone; 0 when log_pt was not solved or its evaluation
+ * at the given position failed).
+ * log_pt >= n_points, log_max_rows > 0 without log_rows, contexts with landmark shards: BA_E_INVALID. */
+#define BA_PTS_STAT_N 8
+typedef struct ba_pts_request {
+    int32_t struct_size, min_obs;        /* BA_PTS_REQUEST_INIT; min_obs <= 0: 1 */
+    const uint8_t* pt_mask;              /* optional [n_points]: non-zero = refine this point; NULL = every point */
+    double* pt_stats;                    /* optional [n_points * BA_PTS_STAT_N] */
+    int32_t log_pt, log_max_rows;        /* log_pt < 0: no log */
+    double* log_rows;                    /* [log_max_rows * BA_LOG_WIDTH], rows as ba_iteration_log, of point log_pt */
+} ba_pts_request;
+typedef struct ba_pts_info {
+    int32_t struct_size, n_selected, n_solved, n_convergence, n_no_convergence, n_failure, max_iterations, log_rows;
+    double time_lm_ms, time_total_ms;    /* the kernel (HIP events); the whole call */
+} ba_pts_info;
+#define BA_PTS_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_pts_request))
+#define BA_PTS_INFO_MIN_SIZE ((int32_t)sizeof(ba_pts_info))
+/* (a zeroed request names point 0 with log_max_rows = 0: no row is written, ba_pts_info.log_rows counts point 0's) */
+#define BA_PTS_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_PTS_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_refine_points(ba_context* ctx, ba_problem* prob, const ba_pts_request* req, ba_pts_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the
