@@ -3,7 +3,8 @@
 // ba_solver.cpp: the C-ABI core and the LM loop; ba_prepare.cpp: ba_prepare's phases (staging, plan, device
 // structure, plan cache); ba_debug.cpp: the ba_debug_* entry points. The stages beside the LM loop, one file each on
 // the scaffold of ba_stage.h: ba_cov.cpp (ba_covariance), ba_resid.cpp (ba_residuals), ba_covis.cpp (ba_covisibility,
-// ba_solve_ordered), ba_local.cpp (ba_local_window, ba_solve_local), ba_loc.cpp (ba_localize).
+// ba_solve_ordered), ba_local.cpp (ba_local_window, ba_solve_local), ba_loc.cpp (ba_localize), ba_pts.cpp (ba_refine_points),
+// ba_pg.cpp (ba_pose_graph).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -107,6 +108,10 @@ enum BufId {
     // ba_refine_points (allocated on its first call): its own copy of the window, the observation indices grouped by
     // point with the points' records, and the statistics, solved positions and log it writes
     B_PTS_IN, B_PTS_IDX, B_PTS_OUT,
+    // ba_pose_graph (allocated on its first call): the graph's copy (poses twice, measurements, weights, endpoints),
+    // the host-built structure (positions, incidence and pair lists), the records / partials / LM state / log, the
+    // dense S, and the blocked Cholesky's own packed envelope, diagonal inverses, padded rhs and block lists
+    B_PG_IN, B_PG_IDX, B_PG_WORK, B_PG_S, B_PG_DENSE_A, B_PG_DENSE_Z, B_PG_DENSE_B, B_PG_DENSE_IDX,
     B_COUNT
 };
 
@@ -195,6 +200,7 @@ struct ba_context {
     hipEvent_t local_ev[2] = {nullptr, nullptr};  // ba_local_window's events around its kernels (first call)
     hipEvent_t loc_ev[2] = {nullptr, nullptr};    // ba_localize's events around its kernel (first call)
     hipEvent_t pts_ev[2] = {nullptr, nullptr};    // ba_refine_points' events around its kernel (first call)
+    hipEvent_t pg_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ba_pose_graph's: an iteration, its reduced solve
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
     int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout
@@ -228,6 +234,8 @@ void flush_prof(ba_context* ctx);
 int apply_spin_limit(ba_context* ctx);
 miba::LmState fresh_state(const ba_options& o, double radius);
 miba::LmParams lm_params(const ba_context* ctx);
+// the termination text of a finished LM state (ba_summary.message)
+void format_message(const miba::LmState& S, char* out, size_t n);
 int enqueue_reset(ba_context* ctx, const miba::LmState& st0, int n_cams);
 int enqueue_iteration_zero(ba_context* ctx);
 int enqueue_iteration(ba_context* ctx, const miba::LmParams& prm);

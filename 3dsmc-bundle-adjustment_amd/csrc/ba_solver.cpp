@@ -136,6 +136,8 @@ void ba_destroy(ba_context* ctx) {
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->pts_ev)
         if (e) hipEventDestroy(e);
+    for (auto& e : ctx->pg_ev)
+        if (e) hipEventDestroy(e);
     if (ctx->prof_events)
         for (int i = 0; i < 2 * Prof::MAXP; ++i) hipEventDestroy(ctx->prof.ev[i]);
     if (ctx->hprog) hipHostFree(ctx->hprog);
@@ -244,7 +246,7 @@ LmState fresh_state(const ba_options& o, double radius) {
     return st;
 }
 
-static void format_message(const LmState& S, char* out, size_t n) {
+void format_message(const LmState& S, char* out, size_t n) {
     switch (S.msg) {
         case MSG_MAX_ITER: std::snprintf(out, n, "Maximum number of iterations reached. Number of iterations: %d.", (int)S.msg_a); break;
         case MSG_GRAD_TOL: std::snprintf(out, n, "Gradient tolerance reached. Gradient max norm: %e <= %e", S.msg_a, S.msg_b); break;

@@ -32,8 +32,8 @@ constexpr const char* kBadIndex = "observation index out of range";
 // shards. req_macro / info_macro are the stems of the header's macros (BA_COV_REQUEST -> BA_COV_REQUEST_MIN_SIZE,
 // BA_COV_REQUEST_INIT); STAGE_SIZES(BA_COV) gives the four arguments. "" when the call may go on.
 #define STAGE_SIZES(stem) stem##_REQUEST_MIN_SIZE, stem##_INFO_MIN_SIZE, #stem "_REQUEST", #stem "_INFO"
-template <class Req, class Info>
-inline std::string stage_refusal(const ba_context* ctx, const ba_problem* p, const Req* req, const Info* info,
+template <class Prob, class Req, class Info>
+inline std::string stage_refusal(const ba_context* ctx, const Prob* p, const Req* req, const Info* info,
                                  int32_t req_min, int32_t info_min, const char* req_macro, const char* info_macro) {
     if (!p || !req || !info) return "null argument";
     auto below = [](const char* what, const char* macro) {

@@ -474,6 +474,80 @@ class BaPtsInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+class BaPgProblem(C.Structure):
+    """Mirror of ``ba_pg_problem`` (ba_pose_graph): a plain struct like ``ba_problem``."""
+
+    _fields_ = [
+        ("n_cams", C.c_int32),
+        ("n_edges", C.c_int32),
+        ("cams", _dp),
+        ("edge_a", _ip),
+        ("edge_b", _ip),
+        ("edge_meas", _dp),
+        ("edge_weight", _dp),
+        ("is_constant", _u8p),
+        ("fixed_cam", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
+class BaPgRequest(C.Structure):
+    """Mirror of ``ba_pg_request``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("log_max_rows", C.c_int32),
+        ("huber", C.c_double),
+        ("log", _dp),
+        ("cam_order", _ip),
+        ("edge_cost", _dp),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaPgInfo(C.Structure):
+    """Mirror of ``ba_pg_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_active", C.c_int32),
+        ("n_edges_used", C.c_int32),
+        ("n_components", C.c_int32),
+        ("band_before", C.c_int32),
+        ("band_after", C.c_int32),
+        ("reduced_system_size", C.c_int32),
+        ("iterations", C.c_int32),
+        ("n_successful", C.c_int32),
+        ("n_unsuccessful", C.c_int32),
+        ("termination_type", C.c_int32),
+        ("log_rows", C.c_int32),
+        ("initial_cost", C.c_double),
+        ("final_cost", C.c_double),
+        ("time_kernels_ms", C.c_double),
+        ("time_solve_ms", C.c_double),
+        ("time_order_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+        ("message", C.c_char * 160),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+        d["message"] = self.message.decode(errors="replace")
+        return d
+
+
+PG_MAX_NPAD = 8192  # BA_PG_MAX_NPAD
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

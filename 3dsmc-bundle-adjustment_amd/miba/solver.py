@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaCovisInfo,
                    BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest, BaLocInfo, BaLocRequest, LOC_STAT_N,
-                   BaPtsInfo, BaPtsRequest, PTS_STAT_N,
+                   BaPtsInfo, BaPtsRequest, PTS_STAT_N, BaPgInfo, BaPgProblem, BaPgRequest,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -242,6 +242,65 @@ class Solver:
         out = info.as_dict()
         out["stats"] = stats[:npt]
         out["log"] = None if log is None else log[: min(info.log_rows, log.shape[0])].copy()
+        return out
+
+    def pose_graph(self, cams, edge_a, edge_b, meas, weights=None, constant=None, fixed_cam: int = -1,
+                   huber: float = 0.0, log: bool = False) -> dict:
+        """ba_pose_graph: Levenberg-Marquardt over the poses ``cams`` (n, 7), updated in place (a float64
+        C-contiguous array; anything else is solved on a copy, returned under ``"cams"``), against the relative-pose
+        edges ``edge_a``, ``edge_b`` (m,), ``meas`` (m, 7) = T_a^-1 T_b, with optional ``weights`` (m, 2) = (w_t, w_r)
+        and a Huber parameter. ``constant`` (indices or a boolean mask) and ``fixed_cam`` name the constant poses. The
+        context's plan and LM state are not touched. Returns the fields of ``ba_pg_info``, ``cams``, ``cam_order``
+        (n,), ``edge_cost`` (m,) and ``log`` (``iteration_log``'s layout; ``None`` unless ``log``)."""
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        x = cams if (isinstance(cams, np.ndarray) and cams.dtype == np.float64 and cams.flags.c_contiguous) else \
+            np.ascontiguousarray(cams, dtype=np.float64)
+        if x.size % 7:
+            raise ValueError("cams must hold 7 values per pose")
+        n = x.size // 7
+        ea = np.ascontiguousarray(edge_a, dtype=np.int32).reshape(-1)
+        eb = np.ascontiguousarray(edge_b, dtype=np.int32).reshape(-1)
+        z = np.ascontiguousarray(meas, dtype=np.float64).reshape(-1, 7)
+        m = len(ea)
+        if len(eb) != m or len(z) != m:
+            raise ValueError("edge_a, edge_b and meas must have one entry per edge")
+        g = BaPgProblem()
+        g.n_cams, g.n_edges, g.fixed_cam = n, m, int(fixed_cam)
+        g.cams = _dptr(x) if n else None
+        if m:
+            g.edge_a, g.edge_b, g.edge_meas = ea.ctypes.data_as(i32p), eb.ctypes.data_as(i32p), _dptr(z)
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1, 2)
+            if len(w) != m:
+                raise ValueError("weights must have one (w_t, w_r) pair per edge")
+            if m:
+                g.edge_weight = _dptr(w)
+        if constant is not None:
+            c = np.asarray(constant)
+            if c.dtype == bool:
+                if c.shape != (n,):
+                    raise ValueError("a boolean constant mask must have one entry per pose")
+                mask = np.ascontiguousarray(c, dtype=np.uint8)
+            else:
+                mask = np.zeros(n, dtype=np.uint8)
+                mask[np.asarray(c, dtype=np.int64).reshape(-1)] = 1
+            if n:
+                g.is_constant = mask.ctypes.data_as(u8p)
+        req, info = BaPgRequest(), BaPgInfo()
+        req.huber = float(huber)
+        order = np.zeros(max(n, 1), dtype=np.int32)
+        ecost = np.zeros(max(m, 1))
+        req.cam_order, req.edge_cost = order.ctypes.data_as(i32p), _dptr(ecost)
+        rows = None
+        if log:
+            rows = np.zeros((max(int(self.options.max_num_iterations), 0) + 1, _lib.LOG_WIDTH))
+            req.log_max_rows, req.log = rows.shape[0], _dptr(rows)
+        self._check(self._L.ba_pose_graph(self._h, C.byref(g), C.byref(req), C.byref(info)), "ba_pose_graph")
+        out = info.as_dict()
+        out["cams"] = x if x.ndim == 2 else x.reshape(-1, 7)
+        out["cam_order"] = order[:n]
+        out["edge_cost"] = ecost[:m]
+        out["log"] = None if rows is None else rows[: min(info.log_rows, rows.shape[0])].copy()
         return out
 
     @staticmethod

@@ -59,7 +59,9 @@ extern "C" {
  *   2, additive  ba_localize with ba_loc_request / ba_loc_info (both sized structs): pose-only refinement of keyframes
  *                against a constant map; ba_options and everything else unchanged.
  *   2, additive  ba_refine_points with ba_pts_request / ba_pts_info (both sized structs): structure-only refinement of
- *                landmarks against constant keyframes; ba_options and everything else unchanged. */
+ *                landmarks against constant keyframes; ba_options and everything else unchanged.
+ *   2, additive  ba_pose_graph with ba_pg_problem, ba_pg_request / ba_pg_info (both sized structs): pose-graph
+ *                optimisation of keyframe poses over relative-pose edges; ba_options and everything else unchanged. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -646,6 +648,81 @@ typedef struct ba_pts_info {
 #define BA_PTS_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 #define BA_PTS_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 int32_t ba_refine_points(ba_context* ctx, ba_problem* prob, const ba_pts_request* req, ba_pts_info* info);
+
+/* ---- pose graph: keyframe poses over relative-pose edges ----
+ * What a SLAM back-end runs when a loop closes, before any bundle adjustment: the accumulated drift is spread over the
+ * keyframes by minimising the disagreement of the poses with a set of relative-pose measurements (sequential odometry,
+ * strong co-visibility, the loop edges). Nodes are the poses of `cams` (ba_problem's layout: quaternion x, y, z, w, then
+ * t, camera-to-world), solved in place; edge k joins edge_a[k] and edge_b[k] and carries the measured relative pose
+ * Z_ab = T_a^-1 T_b in the same layout, with an optional pair (w_t, w_r) in edge_weight: the square roots of the
+ * information of the translation part and of the rotation part (NULL: 1, 1).
+ * Cost. Ceres' pose_graph_3d error term stated for this pose and retraction. For edge (a, b):
+ *   t^ = R_a^T (t_b - t_a),  q^ = q_a^-1 q_b,  dq = q_meas q^^-1 taken on the hemisphere dq.w >= 0 (dq is negated
+ *   when its w is negative: q and -q are one rotation, and the short way round is the one to minimise),
+ *   r = [ w_t (t^ - t_meas) ; w_r 2 vec(dq) ], six values, one residual block per edge.
+ * The cost is 1/2 sum rho(|r|^2): rho trivial for huber = 0, else Ceres' HuberLoss(huber) on the block, with the
+ * sqrt(rho') corrector on residual and Jacobian as the LM kernels apply it to an observation block. Parameters move by
+ * the Sophus right perturbation T exp(delta), delta = [upsilon, omega]; the Jacobians are the exact derivatives of r
+ * with respect to delta_a and delta_b at 0 (no small-angle approximation of the residual).
+ * A pose named by is_constant or fixed_cam is constant: it has no columns, and an edge between two constant poses
+ * counts in the cost only.
+ * Loop. The LM loop of ba_solve for 6 n_active unknowns, every option taken from the context's ba_options: Jacobi
+ * scaling from iteration 0, the clamped LM diagonal over the radius, delta = -scale y, the model cost change
+ * -(delta^T g + delta^T H delta / 2) from the unscaled quantities, rho against min_relative_decrease, the radius update,
+ * invalid steps (a Cholesky pivot that is not positive, a model cost change that is not) with their limit, the three
+ * tolerances with |x| the ambient norm of the active poses, max_num_iterations; the rows of `log` are
+ * ba_iteration_log's.
+ * Linear solve. The normal equations are dense-assembled (npad = 6 n_active rounded up to 16, squared, doubles) and
+ * solved by the blocked multi-workgroup Cholesky of BA_LS_BLOCKED over the envelope the edges leave once the active
+ * poses are placed in reverse Cuthill-McKee order (always: there is no Schur window to protect). A graph with
+ * npad > BA_PG_MAX_NPAD (8192: 1365 active poses, 512 MB) is refused with BA_E_INVALID.
+ * Legal inputs that return 0: no edge, or every pose constant (nothing is written, the costs are reported); an active
+ * pose without an edge (it comes back bitwise as given: its block is the clamped diagonal alone and its step is zero);
+ * a component without a constant pose (the damping keeps the system positive definite; where the poses of such a
+ * component come to rest, the gauge, is then the caller's business).
+ * Outputs. Only active poses are written back; constant poses and every other buffer stay bitwise untouched. No
+ * floating-point atomics, every sum in one fixed order (an edge's position in the caller's arrays): two calls give
+ * the same bits. Stand-alone like ba_localize: device buffers of its own, the context's plan and LM state untouched.
+ * ba_pg_info: n_active poses with columns, n_edges_used edges with an active endpoint, n_components of the active
+ * poses' graph, band_before / band_after (max position distance of two coupled active poses as given / as ordered),
+ * reduced_system_size 6 n_active, the loop's counters, termination_type and message as ba_summary's, log_rows the rows
+ * the loop produced (iterations + 1; the first min(log_rows, log_max_rows) are written), time_kernels_ms the device
+ * time of the LM iterations' kernels and time_solve_ms the reduced solve's part of it (HIP events), time_order_ms the
+ * host's ordering and envelope, time_total_ms the whole call.
+ * Errors. A null argument, struct sizes below the minimum, contexts with landmark shards, negative sizes, a null
+ * required buffer, an edge index out of range, a self edge, fixed_cam >= n_cams, a log without a buffer, the cap:
+ * BA_E_INVALID. A pose, measurement or weight that is not finite: the call returns 0 with termination_type
+ * BA_FAILURE and the evaluation-failed message, the poses kept, no log row (ba_localize's rule). */
+#define BA_PG_MAX_NPAD 8192
+typedef struct ba_pg_problem {
+    int32_t n_cams, n_edges;
+    double* cams;                 /* [n_cams*7] (in/out) */
+    const int32_t* edge_a;        /* [n_edges] */
+    const int32_t* edge_b;        /* [n_edges] */
+    const double* edge_meas;      /* [n_edges*7] Z_ab = T_a^-1 T_b */
+    const double* edge_weight;    /* optional [n_edges*2]: (w_t, w_r); NULL = 1, 1 */
+    const uint8_t* is_constant;   /* optional [n_cams]: non-zero = a constant pose */
+    int32_t fixed_cam, reserved0; /* a further constant pose; -1 = none */
+} ba_pg_problem;
+typedef struct ba_pg_request {
+    int32_t struct_size, log_max_rows;   /* BA_PG_REQUEST_INIT */
+    double huber;                        /* 0: trivial loss; > 0: HuberLoss(huber) on the edge's residual block */
+    double* log;                         /* optional [log_max_rows * BA_LOG_WIDTH], rows as ba_iteration_log */
+    int32_t* cam_order;                  /* optional [n_cams] out: the pose placed k-th (active ones first) */
+    double* edge_cost;                   /* optional [n_edges] out: each edge's robustified cost at the result */
+} ba_pg_request;
+typedef struct ba_pg_info {
+    int32_t struct_size, n_active, n_edges_used, n_components, band_before, band_after, reduced_system_size;
+    int32_t iterations, n_successful, n_unsuccessful, termination_type, log_rows;
+    double initial_cost, final_cost;
+    double time_kernels_ms, time_solve_ms, time_order_ms, time_total_ms;
+    char message[160];
+} ba_pg_info;
+#define BA_PG_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_pg_request))
+#define BA_PG_INFO_MIN_SIZE ((int32_t)sizeof(ba_pg_info))
+#define BA_PG_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_PG_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_pose_graph(ba_context* ctx, ba_pg_problem* g, const ba_pg_request* req, ba_pg_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the
