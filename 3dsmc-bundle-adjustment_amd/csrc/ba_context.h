@@ -112,6 +112,9 @@ enum BufId {
     // the host-built structure (positions, incidence and pair lists), the records / partials / LM state / log, the
     // dense S, and the blocked Cholesky's own packed envelope, diagonal inverses, padded rhs and block lists
     B_PG_IN, B_PG_IDX, B_PG_WORK, B_PG_S, B_PG_DENSE_A, B_PG_DENSE_Z, B_PG_DENSE_B, B_PG_DENSE_IDX,
+    // ba_align (allocated on its first call): its own copy of the correspondences with the pairs' offsets, and what it
+    // writes (poses, statistics, the hypotheses' counts, the inlier mask)
+    B_ALIGN_IN, B_ALIGN_OUT,
     B_COUNT
 };
 
@@ -201,6 +204,7 @@ struct ba_context {
     hipEvent_t loc_ev[2] = {nullptr, nullptr};    // ba_localize's events around its kernel (first call)
     hipEvent_t pts_ev[2] = {nullptr, nullptr};    // ba_refine_points' events around its kernel (first call)
     hipEvent_t pg_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ba_pose_graph's: an iteration, its reduced solve
+    hipEvent_t align_ev[2] = {nullptr, nullptr};  // ba_align's events around its two kernels (first call)
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
     int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout

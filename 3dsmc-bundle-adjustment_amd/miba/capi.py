@@ -548,6 +548,70 @@ class BaPgInfo(C.Structure):
 PG_MAX_NPAD = 8192  # BA_PG_MAX_NPAD
 
 
+class BaAlignProblem(C.Structure):
+    """Mirror of ``ba_align_problem`` (ba_align): a plain struct like ``ba_problem``."""
+
+    _fields_ = [
+        ("n_pairs", C.c_int32),
+        ("n_corr", C.c_int32),
+        ("pair_begin", _ip),
+        ("p1", _dp),
+        ("p2", _dp),
+    ]
+
+
+class BaAlignRequest(C.Structure):
+    """Mirror of ``ba_align_request``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_hypotheses", C.c_int32),
+        ("refit", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("seed", C.c_uint64),
+        ("threshold", C.c_double),
+        ("min_cross", C.c_double),
+        ("probability", C.c_double),
+        ("poses", _dp),
+        ("pair_stats", _dp),
+        ("inlier", _u8p),
+        ("hyp_count", _ip),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaAlignInfo(C.Structure):
+    """Mirror of ``ba_align_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_pairs", C.c_int32),
+        ("n_ok", C.c_int32),
+        ("n_too_few", C.c_int32),
+        ("n_no_model", C.c_int32),
+        ("n_hypotheses", C.c_int32),
+        ("time_kernels_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
+ALIGN_STAT_N = 8  # BA_ALIGN_STAT_N
+ALIGN_MAX_HYP = 65536  # BA_ALIGN_MAX_HYP
+ALIGN_OK, ALIGN_TOO_FEW, ALIGN_NO_MODEL = 0, 1, 2  # BA_ALIGN_OK / _TOO_FEW / _NO_MODEL
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

@@ -7,6 +7,9 @@ Poses are ``ba_problem``'s: ``(qx, qy, qz, qw, tx, ty, tz)``, camera-to-world. A
 * ``relative_pose(Ta, Tb)`` / ``compose(T, Z)``: ``T_a^-1 T_b`` and ``T Z`` (``compose(Ta, relative_pose(Ta, Tb))`` is
   ``Tb``).
 * ``edges_from_poses(cams, pairs)``: the edge arrays ``Solver.pose_graph`` takes, measured on the poses ``cams``.
+* ``measured_edges(prob, pairs, align)``: the same edge arrays measured from the data: for every pair the landmarks
+  both keyframes observe, back-projected into the two camera frames and handed to ``align`` (a
+  ``Solver().align``): the loop-edge measurement, which ``edges_from_poses`` can only read off the drifted poses.
 * ``covis_edges(W, min_weight)``: ORB-SLAM's essential graph from ``Solver.covisibility``'s weights: every pair that
   shares at least ``min_weight`` points, plus a maximum-weight spanning forest of the co-visibility graph so that
   what is connected there stays connected.
@@ -72,6 +75,41 @@ def edges_from_poses(cams, pairs):
     if len(pairs) == 0:
         return ea, eb, np.zeros((0, 7))
     return ea, eb, relative_pose(cams[ea], cams[eb])
+
+
+def measured_edges(prob, pairs, align, min_inliers: int = 20, **kw):
+    """(edge_a, edge_b, meas, n_inliers) of the pairs (m, 2) of keyframes of the window ``prob`` (a ``ProblemArrays``),
+    measured from their shared observations: for a pair (a, b) the landmarks both keyframes observe with an admissible
+    depth (the first such observation of a landmark in each keyframe), back-projected with ``prob.intr`` into a's and
+    b's camera frames -- ``((u - cx) / fx d, (v - cy) / fy d, d)`` -- are the clouds p1 and p2 of one pair of a single
+    ``align(p1, p2, pair_begin, **kw)`` call for all pairs (``align``: a ``miba.solver.Solver().align``). Its pose is
+    ``Z_ab = T_a^-1 T_b``. A pair without a model or with fewer than ``min_inliers`` inliers is dropped."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    fx, fy, cx, cy = (float(v) for v in prob.intr)
+    # per keyframe: landmark -> the back-projection of its first admissible observation
+    local = {}
+    for c in set(pairs.ravel().tolist()):
+        rows = np.nonzero((prob.obs_cam == c) & (prob.obs_depth > 1e-15))[0]
+        pts, first = np.unique(prob.obs_pt[rows], return_index=True)
+        rows = rows[first]
+        d = prob.obs_depth[rows]
+        xyz = np.stack([(prob.obs_uv[rows, 0] - cx) / fx * d, (prob.obs_uv[rows, 1] - cy) / fy * d, d], 1)
+        local[c] = (pts, xyz)
+    p1, p2, begin = [], [], [0]
+    for a, b in pairs:
+        (pa, xa), (pb, xb) = local[int(a)], local[int(b)]
+        _, ia, ib = np.intersect1d(pa, pb, assume_unique=True, return_indices=True)
+        p1.append(xa[ia])
+        p2.append(xb[ib])
+        begin.append(begin[-1] + len(ia))
+    if len(pairs) == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros((0, 7)), np.zeros(0, dtype=np.int64)
+    out = align(np.concatenate(p1).reshape(-1, 3), np.concatenate(p2).reshape(-1, 3), np.array(begin, dtype=np.int32), **kw)
+    stats = np.asarray(out["stats"])
+    n_in = stats[:, 2].astype(np.int64)
+    keep = (stats[:, 0] == 0) & (n_in >= min_inliers)
+    return (pairs[keep, 0].astype(np.int32), pairs[keep, 1].astype(np.int32),
+            np.asarray(out["poses"], dtype=np.float64)[keep], n_in[keep])
 
 
 def covis_edges(W, min_weight: int):

@@ -86,7 +86,7 @@ def make_tum_sequence(n_keyframes: int = 36, n_landmarks: int = 1500, seed: int 
 
 def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_frequency: int = 10,
                  window_size: int = 10, order=None, solve_local=None, min_weight: int = 15, max_local: int = 0,
-                 localize=None, refine_points=None):
+                 localize=None, refine_points=None, align=None):
     """main.cpp:150-195 with one keyframe per frame. Returns (trajectory_text, summaries, intr_opt);
     ``keyframes`` / ``landmarks`` are updated in place. ``order`` (opt-in, default off) goes to
     window.window_optimize: ``"auto"`` solves every window in its co-visibility order. ``solve_local`` (opt-in,
@@ -95,19 +95,25 @@ def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_fre
     default off; a ``Solver().localize``): every keyframe's pose is refined against the map as it stands when the
     keyframe is appended (window.localize_keyframe), before the schedule looks at it. ``refine_points`` (opt-in,
     default off; a ``Solver().refine_points``): right after that, the landmarks the new keyframe re-observes are
-    refined against the keyframes as they stand (window.refine_landmarks)."""
+    refined against the keyframes as they stand (window.refine_landmarks). ``align`` (opt-in, default off; a
+    ``Solver().align``): before any of that, the keyframe's pose is tracked from its 3D-3D matches with the previous
+    keyframe as the reference's tracker does (window.track_keyframe), and the landmarks it is the first to observe are
+    re-placed from that pose."""
     intr_opt = np.array(intr_init, dtype=np.float64)
     summaries = []
     pending = list(keyframes)
     keyframes.clear()
     finished = False
-    seen = set()  # (localize) the landmark ids the keyframes appended so far observe
+    seen = set()  # (align, localize) the landmark ids the keyframes appended so far observe
     while True:
         tracked = bool(pending)  # tracking_step added a keyframe this frame
         if tracked:
             keyframes.append(pending.pop(0))
+            if align is not None:
+                window.track_keyframe(len(keyframes) - 1, keyframes, landmarks, align, seen)
             if localize is not None:
                 window.localize_keyframe(len(keyframes) - 1, keyframes, landmarks, intr_opt, localize, seen)
+            if align is not None or localize is not None:
                 seen.update(keyframes[-1].global_points_map.values())
             if refine_points is not None:
                 window.refine_landmarks(len(keyframes) - 1, keyframes, landmarks, intr_opt, refine_points)

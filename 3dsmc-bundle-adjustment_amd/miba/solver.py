@@ -16,6 +16,7 @@ from . import _lib
 from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaCovInfo, BaCovRequest, BaCovisInfo,
                    BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest, BaLocInfo, BaLocRequest, LOC_STAT_N,
                    BaPtsInfo, BaPtsRequest, PTS_STAT_N, BaPgInfo, BaPgProblem, BaPgRequest,
+                   ALIGN_STAT_N, BaAlignInfo, BaAlignProblem, BaAlignRequest,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -301,6 +302,56 @@ class Solver:
         out["cam_order"] = order[:n]
         out["edge_cost"] = ecost[:m]
         out["log"] = None if rows is None else rows[: min(info.log_rows, rows.shape[0])].copy()
+        return out
+
+    def align(self, p1, p2, pair_begin=None, threshold: float = 0.1, n_hypotheses: int = 256, seed: int = 0,
+              refit: int = 0, min_cross: float = 0.0, probability: float = 0.0, masks: bool = True,
+              counts: bool = False) -> dict:
+        """ba_align: batched RANSAC relative pose from 3D-3D correspondences. ``p1``, ``p2`` (n, 3): matched points
+        in the first and the second frame; ``pair_begin`` (P + 1,): pair j owns the rows [pair_begin[j],
+        pair_begin[j + 1]) (``None``: one pair of all rows). Each pair's pose Z has ``p1 ~ R p2 + t``, which is
+        ``pose_graph``'s ``meas`` Z_ab = T_a^-1 T_b for p1 in a's frame and p2 in b's. ``refit`` rounds re-estimate
+        the best sample's model over its inliers (0: the best minimal sample's model as it is). The context's plan and
+        LM state are not touched. Returns the fields of ``ba_align_info``, ``poses`` (P, 7), ``stats`` (P, 8: status,
+        n, n_inliers, best_hyp, n_degenerate, the inliers' RMS distance, the best sample's n_inliers, k_needed),
+        ``inlier`` (n,) uint8 (``None`` unless ``masks``) and ``hyp_count`` (P, n_hypotheses) int32 (``None`` unless
+        ``counts``)."""
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        a = np.ascontiguousarray(p1, dtype=np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(p2, dtype=np.float64).reshape(-1, 3)
+        if len(a) != len(b):
+            raise ValueError("p1 and p2 must have one row per correspondence")
+        n = len(a)
+        begin = np.array([0, n], dtype=np.int32) if pair_begin is None else \
+            np.ascontiguousarray(pair_begin, dtype=np.int32).reshape(-1)
+        if len(begin) < 1:
+            raise ValueError("pair_begin must have n_pairs + 1 entries")
+        P = len(begin) - 1
+        g = BaAlignProblem()
+        g.n_pairs, g.n_corr = P, n
+        g.pair_begin = begin.ctypes.data_as(i32p)
+        if n:
+            g.p1, g.p2 = _dptr(a), _dptr(b)
+        req, info = BaAlignRequest(), BaAlignInfo()
+        req.n_hypotheses, req.refit, req.seed = int(n_hypotheses), int(refit), int(seed) & 0xFFFFFFFFFFFFFFFF
+        req.threshold, req.min_cross, req.probability = float(threshold), float(min_cross), float(probability)
+        nh = int(n_hypotheses) if int(n_hypotheses) > 0 else 256
+        poses = np.zeros((max(P, 1), 7))
+        stats = np.zeros((max(P, 1), ALIGN_STAT_N))
+        req.poses, req.pair_stats = _dptr(poses), _dptr(stats)
+        mask = hyp = None
+        if masks:
+            mask = np.zeros(max(n, 1), dtype=np.uint8)
+            req.inlier = mask.ctypes.data_as(u8p)
+        if counts and nh <= _lib.ALIGN_MAX_HYP:
+            hyp = np.zeros((max(P, 1), nh), dtype=np.int32)
+            req.hyp_count = hyp.ctypes.data_as(i32p)
+        self._check(self._L.ba_align(self._h, C.byref(g), C.byref(req), C.byref(info)), "ba_align")
+        out = info.as_dict()
+        out["poses"] = poses[:P]
+        out["stats"] = stats[:P]
+        out["inlier"] = None if mask is None else mask[:n]
+        out["hyp_count"] = None if hyp is None else hyp[:P]
         return out
 
     @staticmethod

@@ -168,6 +168,54 @@ def localize_keyframe(k: int, keyframes: list, landmarks: dict, intr, localize, 
     return out
 
 
+def track_matches(k: int, keyframes: list):
+    """The 3D-3D matches of keyframes ``k - 1`` and ``k`` (main.cpp:49-60): the local ids of the two that map to one
+    landmark id with a depth in both, in the order of k's global_points_map; (p1, p2, ids) with p1 / p2 their ``points3d_local`` in frame
+    k - 1 / k."""
+    prev, kf = keyframes[k - 1], keyframes[k]
+    by_landmark = {}
+    for local_id, landmark_id in prev.global_points_map.items():
+        if float(prev.points3d_local[local_id][2]) > 1e-15:
+            by_landmark.setdefault(landmark_id, local_id)
+    p1, p2, ids = [], [], []
+    for local_id, landmark_id in kf.global_points_map.items():
+        if landmark_id in by_landmark and float(kf.points3d_local[local_id][2]) > 1e-15:
+            p1.append(prev.points3d_local[by_landmark[landmark_id]])
+            p2.append(kf.points3d_local[local_id])
+            ids.append(landmark_id)
+    return (np.array(p1, dtype=np.float64).reshape(-1, 3), np.array(p2, dtype=np.float64).reshape(-1, 3), ids)
+
+
+def track_keyframe(k: int, keyframes: list, landmarks: dict, align, seen=None, min_inliers: int = 20, **kw):
+    """The reference tracker's pose of keyframe ``k`` (main.cpp:49-78, initializeRelativePose): ``align`` -- a
+    ``miba.solver.Solver().align`` -- on ``track_matches`` gives T_12 with p1 ~ T_12 p2, and with ``min_inliers`` inliers
+    or more ``T_w_c[k] = T_w_c[k-1] T_12``; with fewer (tracking failed) the pose is kept. The landmarks ``k`` is the
+    first to observe were placed from k's earlier pose, so they are re-placed from the new one
+    (``se3_act(T_new, points3d_local)``) and the map stays consistent with it. ``seen``: the landmark ids keyframes
+    0 .. k-1 observe (``None``: collected here). Returns ``align``'s output with ``tracked`` (bool), or ``None`` for
+    keyframe 0."""
+    if k <= 0:
+        return None
+    p1, p2, _ = track_matches(k, keyframes)
+    out = dict(align(p1, p2, **kw))
+    stats = np.asarray(out["stats"])[0]
+    out["tracked"] = bool(stats[0] == 0 and stats[2] >= min_inliers)
+    if not out["tracked"]:
+        return out
+    kf = keyframes[k]
+    kf.T_w_c = se3_mul(np.array(keyframes[k - 1].T_w_c, dtype=np.float64), np.asarray(out["poses"], dtype=np.float64)[0])
+    if seen is None:
+        seen = set()
+        for other in keyframes[:k]:
+            seen.update(other.global_points_map.values())
+    placed = set()
+    for local_id, landmark_id in kf.global_points_map.items():
+        if landmark_id not in seen and landmark_id not in placed and float(kf.points3d_local[local_id][2]) > 1e-15:
+            landmarks[landmark_id] = se3_act(kf.T_w_c, kf.points3d_local[local_id])
+            placed.add(landmark_id)
+    return out
+
+
 def refine_frame(k: int, keyframes: list, landmarks: dict, intr):
     """The landmarks keyframe ``k`` brings new evidence about, as ``ProblemArrays`` for a structure-only refinement
     (``None`` when nothing qualifies): the landmarks ``k`` observes that an earlier keyframe (index < k) also observes,

@@ -61,7 +61,9 @@ extern "C" {
  *   2, additive  ba_refine_points with ba_pts_request / ba_pts_info (both sized structs): structure-only refinement of
  *                landmarks against constant keyframes; ba_options and everything else unchanged.
  *   2, additive  ba_pose_graph with ba_pg_problem, ba_pg_request / ba_pg_info (both sized structs): pose-graph
- *                optimisation of keyframe poses over relative-pose edges; ba_options and everything else unchanged. */
+ *                optimisation of keyframe poses over relative-pose edges; ba_options and everything else unchanged.
+ *   2, additive  ba_align with ba_align_problem, ba_align_request / ba_align_info (both sized structs): batched RANSAC
+ *                relative pose from 3D-3D correspondences; ba_options and everything else unchanged. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -723,6 +725,87 @@ typedef struct ba_pg_info {
 #define BA_PG_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 #define BA_PG_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 int32_t ba_pose_graph(ba_context* ctx, ba_pg_problem* g, const ba_pg_request* req, ba_pg_info* info);
+
+/* ---- align: batched RANSAC relative pose from 3D-3D correspondences ----
+ * What the tracker runs before anything can be refined (the reference's initializeRelativePose: OpenGV RANSAC over
+ * the matched 3D points of two keyframes), and what measures a loop edge for ba_pose_graph or a start pose for
+ * ba_localize. A call takes n_pairs independent pairs of point clouds: pair j owns the correspondences
+ * [pair_begin[j], pair_begin[j+1]) of p1 / p2 (x, y, z per correspondence, f64); pair_begin is non-decreasing, starts
+ * at 0 or above and ends at n_corr. The result of a pair is the pose Z with p1 ~ R p2 + t in ba_problem's layout
+ * (quaternion x, y, z, w with w >= 0, then t): with p1 in keyframe a's frame and p2 in b's this is ba_pg_problem's
+ * edge_meas Z_ab = T_a^-1 T_b, and the reference's T_1_2.
+ * Hypotheses. Every pair evaluates n_hypotheses minimal samples (<= 0: 256; above BA_ALIGN_MAX_HYP: BA_E_INVALID), all
+ * of them: nothing stops early. The sample of hypothesis h of pair j is integer arithmetic on uint64 alone:
+ *   mix(x):  x += 0x9E3779B97F4A7C15; x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB;
+ *            x ^= x >> 31                                                     (the splitmix64 finaliser)
+ *   key = mix(seed ^ mix((uint64)j << 32 | h)),  r_i = mix(key + i) for i = 1, 2, 3
+ *   d0 = ((r_1 >> 32) * n) >> 32,  d1 = ((r_2 >> 32) * (n - 1)) >> 32,  d2 = ((r_3 >> 32) * (n - 2)) >> 32
+ *   i0 = d0;  i1 = d1, plus 1 if i1 >= i0;  i2 = d2, plus 1 if i2 >= min(i0, i1), then plus 1 if i2 >= max(i0, i1)
+ * with n the pair's size: three distinct indices of the pair, uniform over the ordered triples.
+ * A sample (a, b, c) is degenerate when |(b - a) x (c - a)| <= min_cross (<= 0: 1e-6) in either cloud (compared on the
+ * squares) or when one of its 18 coordinates is not finite; its count is -1. Otherwise its model is Arun's
+ * least-squares fit of the three correspondences: c1, c2 the centroids, H = sum (p2 - c2)(p1 - c1)^T, R the rotation
+ * (det +1) that maximises tr(R H), t = c1 - R c2. R comes from Horn's quaternion form: the eigenvector of the largest
+ * eigenvalue of the symmetric 4x4 matrix built from H, by BA_ALIGN_SWEEPS cyclic Jacobi sweeps. A correspondence is
+ * an inlier of a model when |p1 - (R p2 + t)|^2 < threshold^2 (threshold <= 0: 0.1, the reference's), compared in f64
+ * on the squares; a correspondence with a coordinate that is not finite is never an inlier. hyp_count receives every
+ * hypothesis's inlier count.
+ * Selection. The hypothesis with the largest count wins, the smallest h among equals (OpenGV's strict > keeps the
+ * first). A pair with n < 3 is BA_ALIGN_TOO_FEW (its hyp_count entries are -1), a pair whose every sample is degenerate
+ * BA_ALIGN_NO_MODEL: both return the identity pose, 0 inliers and a zero mask, and the call still returns 0.
+ * Refit, `refit` rounds (0: the reference's behaviour, the best minimal sample's model as it is): Arun's fit over the
+ * current inlier set (the centroids first, then H about them), then the inlier set of the new pose. The round is taken
+ * when its inlier count is >= the previous one, otherwise the rounds end and the previous pose stays; they also end
+ * when a taken round left the set unchanged, when fewer than 3 inliers remain or when the fit is not finite.
+ * pair_stats, BA_ALIGN_STAT_N values per pair:
+ *   [0] status (BA_ALIGN_OK / BA_ALIGN_TOO_FEW / BA_ALIGN_NO_MODEL)   [1] n   [2] n_inliers of the returned pose
+ *   [3] best_hyp (-1 without a model)   [4] n_degenerate samples   [5] the inliers' RMS distance |p1 - (R p2 + t)|
+ *   [6] n_inliers of the best sample before any refit
+ *   [7] k_needed = log(1 - probability) / log(1 - w^3), w = [6] / n (probability <= 0: 0.999): OpenGV's adaptive
+ *   iteration count, computed on the host from the integers, so the caller can see whether n_hypotheses was enough
+ *   (+inf for w = 0, 0 for w = 1 and for a pair without a model).
+ * Reproducibility. No floating-point atomics; every decision is an integer comparison and every sum has one fixed
+ * order set by the pair's size alone: two calls give the same bits, and the pair at index j gives the same bits
+ * whatever the other pairs of the call are (its samples depend on the seed, j and its size alone).
+ * Stand-alone like ba_localize: device buffers of its own, the context's plan and LM state untouched: a
+ * ba_solve_prepared after it is bitwise the solve without it.
+ * ba_align_info: n_pairs, the pairs per status, n_hypotheses as used, time_kernels_ms the two kernels (HIP events),
+ * time_total_ms the whole call. BA_ALIGN_INFO_MIN_SIZE covers the counts; a caller's struct that ends before the
+ * timings is served without them.
+ * Errors, BA_E_INVALID: a null argument, struct sizes below the minimum, contexts with landmark shards, negative
+ * sizes, a pair_begin that is missing, starts below 0, decreases or does not end at n_corr, a null required buffer
+ * (p1 / p2 with n_corr > 0, poses with n_pairs > 0), n_hypotheses above BA_ALIGN_MAX_HYP. */
+#define BA_ALIGN_STAT_N 8
+#define BA_ALIGN_MAX_HYP 65536
+#define BA_ALIGN_SWEEPS 6
+#define BA_ALIGN_OK 0
+#define BA_ALIGN_TOO_FEW 1
+#define BA_ALIGN_NO_MODEL 2
+typedef struct ba_align_problem {
+    int32_t n_pairs, n_corr;
+    const int32_t* pair_begin;    /* [n_pairs+1] */
+    const double* p1;             /* [n_corr*3] */
+    const double* p2;             /* [n_corr*3] */
+} ba_align_problem;
+typedef struct ba_align_request {
+    int32_t struct_size, n_hypotheses;   /* BA_ALIGN_REQUEST_INIT; n_hypotheses <= 0: 256 */
+    int32_t refit, reserved0;            /* refit rounds; 0 = the best sample's model */
+    uint64_t seed;
+    double threshold, min_cross, probability;  /* <= 0: 0.1, 1e-6, 0.999 */
+    double* poses;                       /* [n_pairs*7] out */
+    double* pair_stats;                  /* optional [n_pairs*BA_ALIGN_STAT_N] out */
+    uint8_t* inlier;                     /* optional [n_corr] out: 1 = an inlier of its pair's pose */
+    int32_t* hyp_count;                  /* optional [n_pairs*n_hypotheses] out: inlier counts, -1 = degenerate */
+} ba_align_request;
+typedef struct ba_align_info {
+    int32_t struct_size, n_pairs, n_ok, n_too_few, n_no_model, n_hypotheses;
+    double time_kernels_ms, time_total_ms;
+} ba_align_info;
+#define BA_ALIGN_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_align_request))
+#define BA_ALIGN_INFO_MIN_SIZE ((int32_t)offsetof(ba_align_info, time_kernels_ms))
+#define BA_ALIGN_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_ALIGN_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_align(ba_context* ctx, const ba_align_problem* prob, const ba_align_request* req, ba_align_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the
