@@ -227,6 +227,15 @@ struct ba_context {
         }                                                                                 \
     } while (0)
 
+// The cost constants that come from the options alone: the Huber scales and the LM diagonal's clamp. (The weights
+// sw_r / sw_d / sw_k depend on whose observations are counted: the window's in ba_prepare, a camera's or a point's own
+// in ba_localize / ba_refine_points.)
+inline void cost_consts(const ba_options& o, miba::BaConsts& C) {
+    C.a_r = o.hub_p_repr; C.b_r = o.hub_p_repr * o.hub_p_repr;
+    C.a_d = o.hub_p_unpr; C.b_d = o.hub_p_unpr * o.hub_p_unpr;
+    C.min_diag = o.min_lm_diagonal; C.max_diag = o.max_lm_diagonal;
+}
+
 // ---- ba_prepare.cpp
 // Uploads the window and builds (or reuses) its plan and device structure; the device work is left in flight.
 int prepare(ba_context* ctx, const ba_problem* p);

@@ -353,6 +353,14 @@ static constexpr int RED_X = 16;
 // per-iteration log row: cost, cost_change, |gradient|_inf, |step|, tr_ratio, tr_radius, accepted
 static constexpr int LOG_W = 8;
 
+// One problem of a block LM kernel (ba_block_lm.h: a camera of k_loc_lm, a point of k_pts_lm): its index, its
+// observations idx[begin .. end) of the grouped list and its own weights sqrt(1 / N), sqrt(weight_unpr / N) over its
+// N = end - begin admissible observations
+struct BlockRec {
+    int id, begin, end, pad;
+    double sw_r, sw_d;
+};
+
 struct DevWork {
     double* camdata;
     double* seg_intr;

@@ -14,13 +14,6 @@ static constexpr int LOC_TPB = 256;
 // per workgroup: stats[LOC_STAT] as ba_loc_request.cam_stats
 static constexpr int LOC_STAT = 8;
 
-// One workgroup's camera: its index, its observations idx[begin .. end) and its own weights sqrt(1 / N_c),
-// sqrt(weight_unpr / N_c)
-struct LocCam {
-    int cam, begin, end, pad;
-    double sw_r, sw_d;
-};
-
 struct LocArgs {
     double* cams;           // [n_cams * 7], the solved poses written in place
     const double* pts;      // [n_points * 3]
@@ -29,7 +22,7 @@ struct LocArgs {
     const double* depth;    // [n_obs]
     const int* obs_pt;      // [n_obs]
     const int* idx;         // the observations grouped by camera (ba_loc_group.h)
-    const LocCam* wg;       // [n_wg]
+    const BlockRec* wg;     // [n_wg] one workgroup's camera each
     double* stats;          // [n_wg * LOC_STAT]
     double* log;            // [log_max_rows * LOG_W] of workgroup log_wg (log_wg < 0: none)
     int log_wg, log_max_rows;
@@ -37,7 +30,7 @@ struct LocArgs {
     int jacobi_scaling;
 };
 
-// c: the Huber parameters and the LM diagonal's clamp (sw_r, sw_d come from LocCam); prm: the loop's thresholds
+// c: the Huber parameters and the LM diagonal's clamp (sw_r, sw_d come from BlockRec); prm: the loop's thresholds
 // (prm.progress is not used)
 hipError_t launch_loc_lm(const LocArgs& a, const BaConsts& c, const LmParams& prm, int n_wg, hipStream_t s);
 

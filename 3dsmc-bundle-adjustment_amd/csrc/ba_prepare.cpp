@@ -346,9 +346,7 @@ static void set_consts(ba_context* ctx) {
     C.sw_r = std::sqrt(1.0 / N);             // ReprojectionConstraint weight 1/N (:280)
     C.sw_d = std::sqrt(o.weight_unpr / N);   // DepthPrior WEIGHT_UNPR/N (:290)
     C.sw_k = std::sqrt(o.weight_intrinsics); // IntrinsicsPrior (:238)
-    C.a_r = o.hub_p_repr; C.b_r = o.hub_p_repr * o.hub_p_repr;
-    C.a_d = o.hub_p_unpr; C.b_d = o.hub_p_unpr * o.hub_p_unpr;
-    C.min_diag = o.min_lm_diagonal; C.max_diag = o.max_lm_diagonal;
+    cost_consts(o, C);
 }
 
 // The device state every prepare leaves behind, full or reused: S, rhs and the partial slots cleared, the tail

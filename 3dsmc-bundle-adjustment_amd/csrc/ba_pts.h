@@ -21,13 +21,6 @@ static constexpr int PTS_STAT = 8;
 static_assert(PTS_LANES == 16, "dpp_row_sum sums a DPP row of 16 lanes");
 static_assert(PTS_TPB % 64 == 0 && 64 % PTS_LANES == 0, "whole groups per wave, whole waves per workgroup");
 
-// One group's point: its index, its observations idx[begin .. end) and its own weights sqrt(1 / N_p),
-// sqrt(weight_unpr / N_p)
-struct PtsRec {
-    int pt, begin, end, pad;
-    double sw_r, sw_d;
-};
-
 struct PtsArgs {
     const double* pts;      // [n_points * 3]
     const double* cams;     // [n_cams * 7]
@@ -36,7 +29,7 @@ struct PtsArgs {
     const double* depth;    // [n_obs]
     const int* obs_cam;     // [n_obs]
     const int* idx;         // the observations grouped by point (ba_loc_group.h)
-    const PtsRec* rec;      // [n_rec]
+    const BlockRec* rec;    // [n_rec] one row's point each
     int n_rec;
     double* xout;           // [n_rec * 3] the solved positions, in the records' order
     double* stats;          // [n_rec * PTS_STAT]
@@ -48,7 +41,7 @@ struct PtsArgs {
 
 inline int pts_workgroups(size_t n_rec) { return (int)((n_rec + PTS_PER_WG - 1) / PTS_PER_WG); }
 
-// c: the Huber parameters and the LM diagonal's clamp (sw_r, sw_d come from PtsRec); prm: the loop's thresholds
+// c: the Huber parameters and the LM diagonal's clamp (sw_r, sw_d come from BlockRec); prm: the loop's thresholds
 // (prm.progress is not used)
 hipError_t launch_pts_lm(const PtsArgs& a, const BaConsts& c, const LmParams& prm, hipStream_t s);
 

@@ -1,7 +1,8 @@
 // ba_stage.h — the host scaffold of a stage beside the LM loop (internal): what ba_covariance, ba_residuals,
-// ba_covisibility, ba_local_window / ba_solve_local and ba_localize do before and after their own work. The sized
-// out-structs, the common refusals in their fixed order, the verdict on the problem's sizes / buffers / indices, and
-// the per-call helper (error texts under the entry point's name, device buffers, copies, events).
+// ba_covisibility, ba_local_window / ba_solve_local, ba_localize, ba_refine_points, ba_pose_graph and ba_align do
+// before and after their own work. The sized out-structs, the common refusals in their fixed order, the verdict on the
+// problem's sizes / buffers / indices, and the per-call helper (error texts under the entry point's name, device
+// buffers, copies, events). (ba_localize and ba_refine_points share more than this: ba_block_stage.h.)
 #pragma once
 #include "ba_context.h"
 
