@@ -115,6 +115,9 @@ enum BufId {
     // ba_align (allocated on its first call): its own copy of the correspondences with the pairs' offsets, and what it
     // writes (poses, statistics, the hypotheses' counts, the inlier mask)
     B_ALIGN_IN, B_ALIGN_OUT,
+    // ba_match (allocated on its first call): its own copy of the descriptors with the pairs' ranges and offsets, the
+    // slices' neighbour tables (the swapped launch's beside them), and what it writes
+    B_MATCH_IN, B_MATCH_TOP, B_MATCH_OUT,
     B_COUNT
 };
 
@@ -205,6 +208,8 @@ struct ba_context {
     hipEvent_t pts_ev[2] = {nullptr, nullptr};    // ba_refine_points' events around its kernel (first call)
     hipEvent_t pg_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ba_pose_graph's: an iteration, its reduced solve
     hipEvent_t align_ev[2] = {nullptr, nullptr};  // ba_align's events around its two kernels (first call)
+    hipEvent_t match_ev[2] = {nullptr, nullptr};  // ba_match's events around its kernels (first call)
+    int match_cus = 0;  // the device's compute units, for ba_match's slice count (asked once, at its first call)
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised
     int bcr_retries = 0;        // iterations re-run with the per-level launches after a hand-off timeout

@@ -49,6 +49,7 @@ const Row kTable[] = {
      }},
     {"MIBA_BSFIN", true, [](Settings& s, const char* v) { s.bsfin = is1(v); }},
     {"MIBA_VALUE_CHUNKS", false, [](Settings& s, const char* v) { s.value_chunks = std::max(1, std::min(64, std::atoi(v))); }},
+    {"MIBA_MATCH_SLICES", false, [](Settings& s, const char* v) { s.match_slices = std::max(0, std::atoi(v)); }},
     {"MIBA_PLAN_TIMES", false, [](Settings& s, const char*) { s.plan_times = true; }},
     {"MIBA_PREP_TIMES", false, [](Settings& s, const char*) { s.prep_times = true; }},
 };

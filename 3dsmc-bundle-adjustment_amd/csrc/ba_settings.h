@@ -27,6 +27,9 @@ struct Settings {
     bool blocked_min_set = false;
     long long blocked_min = 0;  // MIBA_BLOCKED_MIN when set
     int value_chunks = 0;  // MIBA_VALUE_CHUNKS (1..64), 0 unset; not keyed
+    // MIBA_MATCH_SLICES (>= 1): ba_match's train slices per query tile, 0 unset; not keyed (ba_match reads the table
+    // at every call: it has no prepare)
+    int match_slices = 0;
     int pp_lanes = 1;      // MIBA_PP_LANES: 1 / 2 / 4 (the launches read their own per-process copy)
     bool plan_times = false, prep_times = false;  // diagnostics on stderr (set at all); not keyed
     unsigned long long key = 0;  // FNV-1a over name and value ("unset" and "" differ) of every keyed variable

@@ -612,6 +612,75 @@ ALIGN_MAX_HYP = 65536  # BA_ALIGN_MAX_HYP
 ALIGN_OK, ALIGN_TOO_FEW, ALIGN_NO_MODEL = 0, 1, 2  # BA_ALIGN_OK / _TOO_FEW / _NO_MODEL
 
 
+class BaMatchProblem(C.Structure):
+    """Mirror of ``ba_match_problem`` (ba_match): a plain struct like ``ba_problem``."""
+
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("desc_bytes", C.c_int32),
+        ("n_query", C.c_int32),
+        ("n_train", C.c_int32),
+        ("n_pairs", C.c_int32),
+        ("n_rows", C.c_int32),
+        ("query", _u8p),
+        ("train", _u8p),
+        ("pair_range", _ip),
+    ]
+
+
+class BaMatchRequest(C.Structure):
+    """Mirror of ``ba_match_request``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("cross_check", C.c_int32),
+        ("ratio", C.c_float),
+        ("max_distance", C.c_int32),
+        ("nn_idx", _ip),
+        ("nn_dist", _ip),
+        ("accept", _u8p),
+        ("matches", _ip),
+        ("match_begin", _ip),
+        ("pair_counts", _ip),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaMatchInfo(C.Structure):
+    """Mirror of ``ba_match_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_pairs", C.c_int32),
+        ("n_rows", C.c_int32),
+        ("n_matches", C.c_int32),
+        ("kind", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("time_kernels_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved0")}
+
+
+MATCH_HAMMING, MATCH_L2_U8 = 0, 1  # BA_MATCH_HAMMING / BA_MATCH_L2_U8
+MATCH_KINDS = {"hamming": MATCH_HAMMING, "l2_u8": MATCH_L2_U8}
+MATCH_MAX_BYTES = 256  # BA_MATCH_MAX_BYTES
+MATCH_COUNT_N = 7  # BA_MATCH_COUNT_N
+# columns of a pair_counts row
+MATCH_COUNT_FIELDS = ("n_q", "n_t", "accepted", "no_second", "ratio", "max_distance", "cross_check")
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

@@ -17,6 +17,7 @@ from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaC
                    BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest, BaLocInfo, BaLocRequest, LOC_STAT_N,
                    BaPtsInfo, BaPtsRequest, PTS_STAT_N, BaPgInfo, BaPgProblem, BaPgRequest,
                    ALIGN_STAT_N, BaAlignInfo, BaAlignProblem, BaAlignRequest,
+                   MATCH_COUNT_N, MATCH_KINDS, BaMatchInfo, BaMatchProblem, BaMatchRequest,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -352,6 +353,62 @@ class Solver:
         out["stats"] = stats[:P]
         out["inlier"] = None if mask is None else mask[:n]
         out["hyp_count"] = None if hyp is None else hyp[:P]
+        return out
+
+    def match(self, query, train, pair_range=None, kind: str = "hamming", ratio: float = 0.7, max_distance: int = 0,
+              cross_check: bool = False, matches: bool = True, counts: bool = False) -> dict:
+        """ba_match: batched 2-nearest-neighbour descriptor matching with Lowe's ratio test. ``query`` (n_query, B),
+        ``train`` (n_train, B) uint8 descriptors of B bytes; ``kind`` ``"hamming"`` (the bytes as bit strings) or
+        ``"l2_u8"`` (the bytes as 0..255, squared Euclidean distances). ``pair_range`` (P, 4): pair j matches the
+        queries [q_begin, q_end) against the trains [t_begin, t_end) (``None``: one pair over everything); ranges may
+        overlap. The context's plan and LM state are not touched. Returns the fields of ``ba_match_info``,
+        ``row_begin`` (P + 1,), ``nn_idx`` / ``nn_dist`` (n_rows, 2) int32 (train indices inside the pair's range, -1 =
+        none), ``accept`` (n_rows,) uint8, ``matches`` (n_matches, 2) int32 (query, train) local to the pair with
+        ``match_begin`` (P + 1,) (``None`` unless ``matches``) and ``pair_counts`` (P, 7: n_q, n_t, accepted, no second
+        neighbour, failed the ratio, failed max_distance, failed the cross-check; ``None`` unless ``counts``)."""
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        if kind not in MATCH_KINDS:
+            raise ValueError(f"kind must be one of {sorted(MATCH_KINDS)}")
+        q = np.ascontiguousarray(query, dtype=np.uint8)
+        t = np.ascontiguousarray(train, dtype=np.uint8)
+        if q.ndim != 2 or t.ndim != 2 or q.shape[1] != t.shape[1]:
+            raise ValueError("query and train must be (n, desc_bytes) arrays of one descriptor size")
+        rng = np.array([[0, len(q), 0, len(t)]], dtype=np.int32) if pair_range is None else \
+            np.ascontiguousarray(pair_range, dtype=np.int32).reshape(-1, 4)
+        P = len(rng)
+        row_begin = np.concatenate([[0], np.cumsum(rng[:, 1].astype(np.int64) - rng[:, 0])])
+        n_rows = int(row_begin[-1])
+        g = BaMatchProblem()
+        g.kind, g.desc_bytes = MATCH_KINDS[kind], q.shape[1]
+        g.n_query, g.n_train, g.n_pairs, g.n_rows = len(q), len(t), P, n_rows
+        if q.size:
+            g.query = q.ctypes.data_as(u8p)
+        if t.size:
+            g.train = t.ctypes.data_as(u8p)
+        if P:
+            g.pair_range = rng.ctypes.data_as(i32p)
+        req, info = BaMatchRequest(), BaMatchInfo()
+        req.cross_check, req.ratio, req.max_distance = int(bool(cross_check)), float(ratio), int(max_distance)
+        rows = max(n_rows, 1)
+        nn_idx = np.zeros((rows, 2), dtype=np.int32)
+        nn_dist = np.zeros((rows, 2), dtype=np.int32)
+        accept = np.zeros(rows, dtype=np.uint8)
+        req.nn_idx, req.nn_dist, req.accept = nn_idx.ctypes.data_as(i32p), nn_dist.ctypes.data_as(i32p), accept.ctypes.data_as(u8p)
+        mlist = mbegin = pcounts = None
+        if matches:
+            mlist = np.zeros((rows, 2), dtype=np.int32)
+            mbegin = np.zeros(P + 1, dtype=np.int32)
+            req.matches, req.match_begin = mlist.ctypes.data_as(i32p), mbegin.ctypes.data_as(i32p)
+        if counts:
+            pcounts = np.zeros((max(P, 1), MATCH_COUNT_N), dtype=np.int32)
+            req.pair_counts = pcounts.ctypes.data_as(i32p)
+        self._check(self._L.ba_match(self._h, C.byref(g), C.byref(req), C.byref(info)), "ba_match")
+        out = info.as_dict()
+        out["row_begin"] = row_begin
+        out["nn_idx"], out["nn_dist"], out["accept"] = nn_idx[:n_rows], nn_dist[:n_rows], accept[:n_rows]
+        out["matches"] = None if mlist is None else mlist[: info.n_matches]
+        out["match_begin"] = mbegin
+        out["pair_counts"] = None if pcounts is None else pcounts[:P]
         return out
 
     @staticmethod

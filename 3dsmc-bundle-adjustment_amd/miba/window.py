@@ -13,6 +13,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import matching
 from .capi import ProblemArrays
 
 
@@ -61,6 +62,7 @@ class KeyFrame:
     points3d_local: np.ndarray  # (K, 3)
     global_points_map: dict = field(default_factory=dict)  # localId -> LandmarkId (iteration order kept)
     timestamp: str = ""
+    descriptors: np.ndarray | None = None  # (K, B) uint8, one row per keypoint (miba.matching.attach_descriptors)
 
 
 def window_optimize(kf_i: int, kf_f: int, keyframes: list, landmarks: dict, intr_init, intr_opt: np.ndarray,
@@ -186,17 +188,24 @@ def track_matches(k: int, keyframes: list):
     return (np.array(p1, dtype=np.float64).reshape(-1, 3), np.array(p2, dtype=np.float64).reshape(-1, 3), ids)
 
 
-def track_keyframe(k: int, keyframes: list, landmarks: dict, align, seen=None, min_inliers: int = 20, **kw):
+def track_keyframe(k: int, keyframes: list, landmarks: dict, align, seen=None, min_inliers: int = 20, match=None, **kw):
     """The reference tracker's pose of keyframe ``k`` (main.cpp:49-78, initializeRelativePose): ``align`` -- a
     ``miba.solver.Solver().align`` -- on ``track_matches`` gives T_12 with p1 ~ T_12 p2, and with ``min_inliers`` inliers
     or more ``T_w_c[k] = T_w_c[k-1] T_12``; with fewer (tracking failed) the pose is kept. The landmarks ``k`` is the
     first to observe were placed from k's earlier pose, so they are re-placed from the new one
     (``se3_act(T_new, points3d_local)``) and the map stays consistent with it. ``seen``: the landmark ids keyframes
-    0 .. k-1 observe (``None``: collected here). Returns ``align``'s output with ``tracked`` (bool), or ``None`` for
-    keyframe 0."""
+    0 .. k-1 observe (``None``: collected here). ``match`` (opt-in, default off; a ``miba.solver.Solver().match``): when
+    both keyframes carry descriptors the matches come from them as the reference's do (matchKeypoints +
+    filterMatchesLowe, the previous keyframe's descriptors as the queries; ``matching.correspondences``) in place of
+    ``track_matches``' landmark ids. Returns ``align``'s output with ``tracked`` (bool), or ``None`` for keyframe 0."""
     if k <= 0:
         return None
-    p1, p2, _ = track_matches(k, keyframes)
+    prev, cur = keyframes[k - 1], keyframes[k]
+    if match is not None and prev.descriptors is not None and cur.descriptors is not None:
+        p1, p2 = matching.correspondences(match(prev.descriptors, cur.descriptors), 0, prev.points3d_local,
+                                          cur.points3d_local)
+    else:
+        p1, p2, _ = track_matches(k, keyframes)
     out = dict(align(p1, p2, **kw))
     stats = np.asarray(out["stats"])[0]
     out["tracked"] = bool(stats[0] == 0 and stats[2] >= min_inliers)

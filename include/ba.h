@@ -63,7 +63,9 @@ extern "C" {
  *   2, additive  ba_pose_graph with ba_pg_problem, ba_pg_request / ba_pg_info (both sized structs): pose-graph
  *                optimisation of keyframe poses over relative-pose edges; ba_options and everything else unchanged.
  *   2, additive  ba_align with ba_align_problem, ba_align_request / ba_align_info (both sized structs): batched RANSAC
- *                relative pose from 3D-3D correspondences; ba_options and everything else unchanged. */
+ *                relative pose from 3D-3D correspondences; ba_options and everything else unchanged.
+ *   2, additive  ba_match with ba_match_problem, ba_match_request / ba_match_info (both sized structs): batched
+ *                2-nearest-neighbour descriptor matching with the ratio test; everything else unchanged. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -806,6 +808,82 @@ typedef struct ba_align_info {
 #define BA_ALIGN_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 #define BA_ALIGN_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 int32_t ba_align(ba_context* ctx, const ba_align_problem* prob, const ba_align_request* req, ba_align_info* info);
+
+/* ---- match: batched 2-nearest-neighbour descriptor matching with the ratio test ----
+ * What finds the correspondences ba_align starts from (the reference's matchKeypoints + filterMatchesLowe: OpenCV's
+ * brute-force knnMatch with k = 2, then Lowe's ratio test). A call takes n_pairs independent pairs of descriptor
+ * sets. A descriptor is desc_bytes bytes; kind says how two of them compare:
+ *   BA_MATCH_HAMMING  the bytes as bit strings, distance = popcount(a xor b)                      (ORB, BRIEF)
+ *   BA_MATCH_L2_U8    the bytes as the integers 0..255, distance = sum (a_k - b_k)^2, an exact int32: the SQUARE of
+ *                     the Euclidean distance (byte SIFT)
+ * Rows. Pair j's queries are query[q_begin..q_end) and its trains train[t_begin..t_end) (pair_range, four values per
+ * pair; descriptor indices). Ranges of different pairs may overlap: one keyframe against many candidates is one copy
+ * of its descriptors. Output row row_begin[j] + (q - q_begin) belongs to query q of pair j, with row_begin[j] the sum
+ * of (q_end - q_begin) over the pairs before j; n_rows is that sum over all pairs.
+ * Neighbours. The first and the second neighbour of a query are the two smallest trains of its pair under the
+ * lexicographic order (distance, train index). The definition does not depend on any traversal order: a tile, a slice
+ * and a merge of slices all give the same answer. Among equal distances the smaller index is first (OpenCV's
+ * brute-force knnMatch with its strict <). nn_idx holds the two train indices inside the pair's range (t - t_begin),
+ * nn_dist their distances; a pair with one train has no second neighbour, a pair with none has neither: -1 in both.
+ * Acceptance. The conditions are checked in this order and a query is counted at the first one it fails:
+ *   1. a second neighbour exists;
+ *   2. the ratio test (ratio <= 0: 0.7, the reference's): HAMMING (float)d0 < ratio * (float)d1 evaluated in f32,
+ *      which is filterMatchesLowe on OpenCV's float distances bit for bit; L2_U8 on the squares in f64,
+ *      (double)s0 < ((double)ratio * (double)ratio) * (double)s1, which equals the reference's test on the square
+ *      roots except where the two sides meet within rounding;
+ *   3. d0 <= max_distance, if max_distance > 0 (for L2_U8 on the squared distance, as nn_dist holds it);
+ *   4. with cross_check: the query is the smallest query of its pair, under (distance, query index), for the train
+ *      it chose.
+ * accept is 1 for a row that passes all of them. matches lists the accepted rows of each pair in query order as
+ * (query, train), both local to the pair's ranges; pair j's are matches[2 match_begin[j] .. 2 match_begin[j+1]).
+ * pair_counts, BA_MATCH_COUNT_N values per pair:
+ *   [0] n_q   [1] n_t   [2] accepted   [3] no second neighbour   [4] failed the ratio   [5] failed max_distance
+ *   [6] failed the cross-check                                                 ([2] + .. + [6] = [0])
+ * Reproducibility. Only integer arithmetic and integer atomics are used (the ratio test is one product and one
+ * comparison per row): two calls give the same bits, and a pair's rows give the same bits whatever the other pairs of
+ * the call are and however the trains are sliced over workgroups.
+ * Stand-alone like ba_align: device buffers of its own, the context's plan and LM state untouched: a
+ * ba_solve_prepared after it is bitwise the solve without it.
+ * ba_match_info: n_pairs, n_rows, n_matches (the accepted rows of all pairs), kind, time_kernels_ms the kernels (HIP
+ * events), time_total_ms the whole call. BA_MATCH_INFO_MIN_SIZE covers the counts; a caller's struct that ends before
+ * the timings is served without them.
+ * Errors, BA_E_INVALID: a null argument, struct sizes below the minimum, contexts with landmark shards; then negative
+ * sizes; a kind or desc_bytes outside the above; a range that is reversed or leaves [0, n_query) / [0, n_train);
+ * n_rows that is not the sum of the pairs' query counts; a null required buffer (query / train with rows to read,
+ * pair_range with pairs, nn_idx / nn_dist with rows, match_begin with matches); a grid above the launch limit of 2^32
+ * threads (2^26 workgroups of 64 queries x train slices for HAMMING, 2^24 for L2_U8: some 10^9 rows). Empty pairs and
+ * n_pairs = 0 return 0. */
+#define BA_MATCH_HAMMING 0      /* bytes as bit strings: distance = popcount(a xor b)                    */
+#define BA_MATCH_L2_U8   1      /* bytes as 0..255: distance = sum (a_k - b_k)^2, an exact int32         */
+#define BA_MATCH_MAX_BYTES 256
+#define BA_MATCH_COUNT_N 7
+typedef struct ba_match_problem {
+    int32_t kind, desc_bytes;          /* desc_bytes: a multiple of 4 in [4, BA_MATCH_MAX_BYTES]          */
+    int32_t n_query, n_train;          /* descriptors in query / train                                    */
+    int32_t n_pairs, n_rows;           /* n_rows = sum over pairs of (q_end - q_begin)                    */
+    const uint8_t* query;              /* [n_query*desc_bytes]                                            */
+    const uint8_t* train;              /* [n_train*desc_bytes]                                            */
+    const int32_t* pair_range;         /* [n_pairs*4]: q_begin, q_end, t_begin, t_end                     */
+} ba_match_problem;
+typedef struct ba_match_request {
+    int32_t struct_size, cross_check;  /* BA_MATCH_REQUEST_INIT; cross_check 0 = the reference            */
+    float ratio; int32_t max_distance; /* ratio <= 0: 0.7f; max_distance <= 0: no limit                   */
+    int32_t* nn_idx;                   /* [n_rows*2] out: train index inside the pair's range, -1 = none  */
+    int32_t* nn_dist;                  /* [n_rows*2] out: the distances, -1 = none                        */
+    uint8_t* accept;                   /* optional [n_rows] out                                           */
+    int32_t* matches;                  /* optional [n_rows*2] out: accepted (query, train), both local to the pair */
+    int32_t* match_begin;              /* optional [n_pairs+1] out (required with matches)                */
+    int32_t* pair_counts;              /* optional [n_pairs*BA_MATCH_COUNT_N] out                         */
+} ba_match_request;
+typedef struct ba_match_info {
+    int32_t struct_size, n_pairs, n_rows, n_matches, kind, reserved0;
+    double time_kernels_ms, time_total_ms;
+} ba_match_info;
+#define BA_MATCH_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_match_request))
+#define BA_MATCH_INFO_MIN_SIZE ((int32_t)offsetof(ba_match_info, time_kernels_ms))
+#define BA_MATCH_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_MATCH_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_match(ba_context* ctx, const ba_match_problem* prob, const ba_match_request* req, ba_match_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the
