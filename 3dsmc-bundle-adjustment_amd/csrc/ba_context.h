@@ -4,7 +4,7 @@
 // structure, plan cache); ba_debug.cpp: the ba_debug_* entry points. The stages beside the LM loop, one file each on
 // the scaffold of ba_stage.h: ba_cov.cpp (ba_covariance), ba_resid.cpp (ba_residuals), ba_covis.cpp (ba_covisibility,
 // ba_solve_ordered), ba_local.cpp (ba_local_window, ba_solve_local), ba_loc.cpp (ba_localize), ba_pts.cpp (ba_refine_points),
-// ba_pg.cpp (ba_pose_graph).
+// ba_pg.cpp (ba_pose_graph), ba_align.cpp (ba_align), ba_match.cpp (ba_match), ba_gmatch.cpp (ba_guided_match).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -118,6 +118,9 @@ enum BufId {
     // ba_match (allocated on its first call): its own copy of the descriptors with the pairs' ranges and offsets, the
     // slices' neighbour tables (the swapped launch's beside them), and what it writes
     B_MATCH_IN, B_MATCH_TOP, B_MATCH_OUT,
+    // ba_guided_match (allocated on its first call): its own copy of the keypoints, landmarks, frames and candidates
+    // with the host's layout, the binned keypoint grids with the one-to-one table, and what it writes
+    B_GMATCH_IN, B_GMATCH_GRID, B_GMATCH_OUT,
     B_COUNT
 };
 
@@ -209,6 +212,7 @@ struct ba_context {
     hipEvent_t pg_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ba_pose_graph's: an iteration, its reduced solve
     hipEvent_t align_ev[2] = {nullptr, nullptr};  // ba_align's events around its two kernels (first call)
     hipEvent_t match_ev[2] = {nullptr, nullptr};  // ba_match's events around its kernels (first call)
+    hipEvent_t gmatch_ev[2] = {nullptr, nullptr};  // ba_guided_match's events around its kernels (first call)
     int match_cus = 0;  // the device's compute units, for ba_match's slice count (asked once, at its first call)
     bool bcr_fallback = false;  // a resident BCR kernel timed out: per-level launches from then on
     unsigned long long bcr_launches = 0;  // split-kernel launches since the BCR workspace was initialised

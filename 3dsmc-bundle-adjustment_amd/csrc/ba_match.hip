@@ -2,6 +2,7 @@
 // the acceptance chain, then the ordered compaction. Integers throughout.
 #include "ba_match.h"
 #include "ba_scan.h"
+#include "ba_top2.h"
 
 #include "../../include/ba.h"
 
@@ -13,33 +14,10 @@ static_assert(MATCH_SCAN_TPB == SCAN_TPB, "the host's launch limit counts ba_sca
 
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 
-// the running top-2 under the packed key: k0 < k1 always (the keys of one query are distinct by their index)
-__device__ __forceinline__ void top2_push(unsigned long long key, unsigned long long& k0, unsigned long long& k1) {
-    const unsigned long long hi = key > k0 ? key : k0;
-    k0 = key < k0 ? key : k0;
-    k1 = hi < k1 ? hi : k1;
-}
-__device__ __forceinline__ void top2_merge(unsigned long long b0, unsigned long long b1, unsigned long long& k0,
-                                           unsigned long long& k1) {
-    const unsigned long long hi = b0 > k0 ? b0 : k0, lo1 = b1 < k1 ? b1 : k1;
-    k0 = b0 < k0 ? b0 : k0;
-    k1 = hi < lo1 ? hi : lo1;
-}
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
     const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m, 64);
     const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, 64);
     return (unsigned long long)hi << 32 | lo;
-}
-
-// the largest j in [0, n) with begin[j] <= x (begin is non-decreasing, begin[0] <= x < begin[n])
-template <class T>
-__device__ __forceinline__ int owner_of(const T* begin, int n, T x) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (begin[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // What a workgroup of k_match_nn works on: its pair, its queries and its slice of the pair's trains.

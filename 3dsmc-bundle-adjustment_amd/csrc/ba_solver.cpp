@@ -142,6 +142,8 @@ void ba_destroy(ba_context* ctx) {
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->match_ev)
         if (e) hipEventDestroy(e);
+    for (auto& e : ctx->gmatch_ev)
+        if (e) hipEventDestroy(e);
     if (ctx->prof_events)
         for (int i = 0; i < 2 * Prof::MAXP; ++i) hipEventDestroy(ctx->prof.ev[i]);
     if (ctx->hprog) hipHostFree(ctx->hprog);

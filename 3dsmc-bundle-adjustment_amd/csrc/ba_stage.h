@@ -1,5 +1,6 @@
 // ba_stage.h — the host scaffold of a stage beside the LM loop (internal): what ba_covariance, ba_residuals,
-// ba_covisibility, ba_local_window / ba_solve_local, ba_localize, ba_refine_points, ba_pose_graph, ba_align and ba_match do
+// ba_covisibility, ba_local_window / ba_solve_local, ba_localize, ba_refine_points, ba_pose_graph, ba_align, ba_match and
+// ba_guided_match do
 // before and after their own work. The sized out-structs, the common refusals in their fixed order, the verdict on the
 // problem's sizes / buffers / indices, and the per-call helper (error texts under the entry point's name, device
 // buffers, copies, events). (ba_localize and ba_refine_points share more than this: ba_block_stage.h.)

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 import subprocess
 
-from .capi import BaAlignInfo, BaAlignProblem, BaAlignRequest, BaCovInfo, BaCovRequest, BaCovisInfo, BaCovisRequest, BaKernelStat, BaLocalInfo, BaLocalRequest, BaLocInfo, BaLocRequest, BaMatchInfo, BaMatchProblem, BaMatchRequest, BaPgInfo, BaPgProblem, BaPgRequest, BaPtsInfo, BaPtsRequest, BaResInfo, BaResRequest, BaOptions, BaPrepareInfo, BaProblem, BaSummary
+from .capi import BaAlignInfo, BaAlignProblem, BaAlignRequest, BaCovInfo, BaCovRequest, BaCovisInfo, BaCovisRequest, BaGmatchInfo, BaGmatchProblem, BaGmatchRequest, BaKernelStat, BaLocalInfo, BaLocalRequest, BaLocInfo, BaLocRequest, BaMatchInfo, BaMatchProblem, BaMatchRequest, BaPgInfo, BaPgProblem, BaPgRequest, BaPtsInfo, BaPtsRequest, BaResInfo, BaResRequest, BaOptions, BaPrepareInfo, BaProblem, BaSummary
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("MIBA_LIB_PATH") or os.path.join(PKG_DIR, "lib", "libmiba.so")  # override: A/B builds
@@ -19,7 +19,7 @@ EXPORTS = (
     "ba_debug_linearize", "ba_debug_reduced_system", "ba_debug_camera_sums", "ba_debug_plan_digest", "ba_debug_step", "ba_debug_step_state", "ba_comm_unique_id", "ba_comm_init", "ba_comm_init_host",
     "ba_iteration_log", "ba_last_prepare", "ba_covariance", "ba_residuals", "ba_covisibility", "ba_solve_ordered",
     "ba_set_constant_cameras", "ba_local_window", "ba_solve_local", "ba_localize", "ba_refine_points",
-    "ba_pose_graph", "ba_align", "ba_match",
+    "ba_pose_graph", "ba_align", "ba_match", "ba_guided_match",
     "ba_problem_write", "ba_problem_read_dims", "ba_problem_read", "ba_bal_read_dims", "ba_bal_read", "ba_bal_write",
 )
 COMM_ID_BYTES = 128  # BA_COMM_ID_BYTES
@@ -116,6 +116,8 @@ def lib():
     L.ba_align.restype = C.c_int32
     L.ba_match.argtypes = [C.c_void_p, C.POINTER(BaMatchProblem), C.POINTER(BaMatchRequest), C.POINTER(BaMatchInfo)]
     L.ba_match.restype = C.c_int32
+    L.ba_guided_match.argtypes = [C.c_void_p, C.POINTER(BaGmatchProblem), C.POINTER(BaGmatchRequest), C.POINTER(BaGmatchInfo)]
+    L.ba_guided_match.restype = C.c_int32
     ip = C.POINTER(C.c_int32)
     L.ba_problem_write.argtypes = [C.c_char_p, C.POINTER(BaProblem), C.POINTER(BaOptions)]
     L.ba_problem_read_dims.argtypes = [C.c_char_p, ip, ip, ip]

@@ -681,6 +681,93 @@ MATCH_COUNT_N = 7  # BA_MATCH_COUNT_N
 MATCH_COUNT_FIELDS = ("n_q", "n_t", "accepted", "no_second", "ratio", "max_distance", "cross_check")
 
 
+class BaGmatchProblem(C.Structure):
+    """Mirror of ``ba_gmatch_problem`` (ba_guided_match): a plain struct like ``ba_match_problem``."""
+
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("desc_bytes", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("n_kp", C.c_int32),
+        ("n_points", C.c_int32),
+        ("n_frames", C.c_int32),
+        ("n_rows", C.c_int32),
+        ("intr", C.c_double * 4),
+        ("kp_uv", _dp),
+        ("kp_desc", _u8p),
+        ("kp_depth", _dp),
+        ("points", _dp),
+        ("pt_desc", _u8p),
+        ("frame_pose", _dp),
+        ("frame_range", _ip),
+        ("cand_begin", _ip),
+        ("cand_pt", _ip),
+    ]
+
+
+class BaGmatchRequest(C.Structure):
+    """Mirror of ``ba_gmatch_request``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("one_to_one", C.c_int32),
+        ("radius", C.c_double),
+        ("ratio", C.c_float),
+        ("max_distance", C.c_int32),
+        ("min_depth", C.c_double),
+        ("depth_tol", C.c_double),
+        ("cell_px", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("nn_kp", _ip),
+        ("nn_dist", _ip),
+        ("status", _u8p),
+        ("proj", _dp),
+        ("n_in_window", _ip),
+        ("matches", _ip),
+        ("match_begin", _ip),
+        ("frame_counts", _ip),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class BaGmatchInfo(C.Structure):
+    """Mirror of ``ba_gmatch_info``. ``struct_size`` is set to this mirror's size on construction."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_frames", C.c_int32),
+        ("n_rows", C.c_int32),
+        ("n_matches", C.c_int32),
+        ("kind", C.c_int32),
+        ("n_grids", C.c_int32),
+        ("cell_px", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("time_kernels_ms", C.c_double),
+        ("time_total_ms", C.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved0")}
+
+
+GMATCH_COUNT_N = 9  # BA_GMATCH_COUNT_N
+# columns of a frame_counts row: the candidates, the keypoints of the range, then the rows of every status value
+GMATCH_COUNT_FIELDS = ("n_cand", "n_kp", "accepted", "behind", "outside", "empty_window", "ratio", "max_distance",
+                       "one_to_one")
+# ba_guided_match's status values, by name
+GMATCH_STATUS = {name: i for i, name in enumerate(GMATCH_COUNT_FIELDS[2:])}
+
+
 def default_options_py() -> BaOptions:
     """Pure-Python defaults (used only where no compiled library is loaded)."""
     o = BaOptions()

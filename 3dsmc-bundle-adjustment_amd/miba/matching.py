@@ -7,7 +7,10 @@ correspondences ``Solver.align`` starts from (the reference's matchKeypoints + f
   with the reference's depth filter.
 * ``matched_edges(keyframes, pairs, match, align)``: relative-pose edges between keyframes from their descriptors
   alone, the counterpart of ``posegraph.measured_edges`` for keyframes that share no landmark id (a revisit the map
-  does not know about: the loops that need closing)."""
+  does not know about: the loops that need closing).
+* ``landmark_descriptors(keyframes)``: one descriptor per landmark id, for ``Solver.guided_match`` (ba_guided_match).
+* ``fuse_landmarks(keyframes, landmarks, pairs, ...)``: after such a loop is closed, the landmarks keyframe a observes
+  are searched for in keyframe b by projection; what is found adds an observation or merges two ids of one point."""
 from __future__ import annotations
 
 import numpy as np
@@ -90,3 +93,90 @@ def matched_edges(keyframes, pairs, match, align, min_inliers: int = 20, match_k
     keep = (stats[:, 0] == 0) & (n_in >= min_inliers)
     return (pairs[keep, 0].astype(np.int32), pairs[keep, 1].astype(np.int32),
             np.asarray(res["poses"], dtype=np.float64)[keep], n_in[keep])
+
+
+def landmark_descriptors(keyframes):
+    """(ids, desc): every landmark id the keyframes observe, in the order of its first observation (keyframe order,
+    then the order of ``global_points_map``), with the descriptor of that first observation. ids (n,) int64, desc
+    (n, B) uint8. Keyframes without descriptors are passed over."""
+    ids, desc, have = [], [], set()
+    for kf in keyframes:
+        if kf.descriptors is None:
+            continue
+        for local_id, landmark_id in kf.global_points_map.items():
+            if landmark_id not in have:
+                have.add(landmark_id)
+                ids.append(landmark_id)
+                desc.append(kf.descriptors[local_id])
+    nbytes = next((kf.descriptors.shape[1] for kf in keyframes if kf.descriptors is not None), 0)
+    return np.array(ids, dtype=np.int64), np.array(desc, dtype=np.uint8).reshape(-1, nbytes)
+
+
+def fuse_landmarks(keyframes, landmarks, pairs, intr, width: int, height: int, guided_match, **kw):
+    """ORB-SLAM's Fuse after a loop closure: for each (a, b) of ``pairs`` the landmarks keyframe a observes (and b does
+    not) are projected into keyframe b with the poses and the map as they stand, and searched for among all of b's
+    keypoints: one ``guided_match(points, pt_desc, kp_uv, kp_desc, frame_pose, intr, width, height, frame_range=...,
+    cand=..., kp_depth=..., **kw)`` call for all pairs (a ``miba.solver.Solver().guided_match``; every keyframe b's
+    keypoints are in the call once). The accepted matches are applied in the order of the pairs: a match on a keypoint
+    that maps to no landmark adds the observation to b's ``global_points_map`` (unless b observes that landmark by
+    then); a match on a keypoint that maps to another id merges the two: the landmark with more observations is kept
+    (on a tie the smaller id), every ``global_points_map`` entry of the other is rewritten to it and the other is
+    dropped from ``landmarks``. Returns the merges as (kept id, dropped id) in the order they were made."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pairs) == 0:
+        return []
+    ids, desc = landmark_descriptors(keyframes)
+    row = {int(l): i for i, l in enumerate(ids)}
+    targets = sorted(set(pairs[:, 1].tolist()))
+    begin, at = {}, 0
+    for b in targets:
+        begin[b] = at
+        at += len(keyframes[b].keypoints)
+    kp_uv = np.concatenate([np.asarray(keyframes[b].keypoints, dtype=np.float64).reshape(-1, 2) for b in targets])
+    kp_desc = np.concatenate([np.asarray(keyframes[b].descriptors, dtype=np.uint8) for b in targets])
+    kp_depth = np.concatenate([np.asarray(keyframes[b].points3d_local, dtype=np.float64).reshape(-1, 3)[:, 2] for b in targets])
+    points = np.array([landmarks[int(l)] for l in ids], dtype=np.float64).reshape(-1, 3)
+    cand, poses, ranges = [], [], []
+    for a, b in pairs.tolist():
+        in_b = set(keyframes[b].global_points_map.values())
+        seen, c = set(), []
+        for landmark_id in keyframes[a].global_points_map.values():
+            if landmark_id not in in_b and landmark_id not in seen:
+                seen.add(landmark_id)
+                c.append(row[landmark_id])
+        cand.append(np.array(c, dtype=np.int32))
+        poses.append(np.asarray(keyframes[b].T_w_c, dtype=np.float64))
+        ranges.append((begin[b], begin[b] + len(keyframes[b].keypoints)))
+    out = guided_match(points, desc, kp_uv, kp_desc, np.array(poses).reshape(-1, 7), intr, width, height,
+                       frame_range=np.array(ranges, dtype=np.int32), cand=cand, kp_depth=kp_depth, **kw)
+    alias, merges = {}, []
+
+    def current(landmark_id):
+        while landmark_id in alias:
+            landmark_id = alias[landmark_id]
+        return landmark_id
+
+    def n_obs(landmark_id):
+        return sum(1 for kf in keyframes for g in kf.global_points_map.values() if g == landmark_id)
+
+    for j, (a, b) in enumerate(pairs.tolist()):
+        gpm = keyframes[b].global_points_map
+        for pt, kp in np.asarray(out["matches"])[int(out["match_begin"][j]):int(out["match_begin"][j + 1])].tolist():
+            found = current(int(ids[pt]))
+            there = gpm.get(kp)
+            if there is None:
+                if found not in gpm.values():
+                    gpm[kp] = found
+                continue
+            if there == found:
+                continue
+            na, nb = n_obs(found), n_obs(there)
+            keep, drop = (found, there) if (na, -found) > (nb, -there) else (there, found)
+            for kf in keyframes:
+                for local_id, g in kf.global_points_map.items():
+                    if g == drop:
+                        kf.global_points_map[local_id] = keep
+            landmarks.pop(drop, None)
+            alias[drop] = keep
+            merges.append((keep, drop))
+    return merges

@@ -86,7 +86,7 @@ def make_tum_sequence(n_keyframes: int = 36, n_landmarks: int = 1500, seed: int 
 
 def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_frequency: int = 10,
                  window_size: int = 10, order=None, solve_local=None, min_weight: int = 15, max_local: int = 0,
-                 localize=None, refine_points=None, align=None, match=None):
+                 localize=None, refine_points=None, align=None, match=None, search=None):
     """main.cpp:150-195 with one keyframe per frame. Returns (trajectory_text, summaries, intr_opt);
     ``keyframes`` / ``landmarks`` are updated in place. ``order`` (opt-in, default off) goes to
     window.window_optimize: ``"auto"`` solves every window in its co-visibility order. ``solve_local`` (opt-in,
@@ -100,7 +100,10 @@ def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_fre
     keyframe as the reference's tracker does (window.track_keyframe), and the landmarks it is the first to observe are
     re-placed from that pose. ``match`` (opt-in, default off; a ``Solver().match``): with ``align``, and for keyframes
     that carry descriptors (matching.attach_descriptors), those matches come from the descriptors (ba_match) instead
-    of the landmark ids."""
+    of the landmark ids. ``search`` (opt-in, default off; a ``Solver().guided_match``): after the tracking and before
+    ``localize``, the landmarks the last few keyframes observe and the new one does not are searched for in it by
+    projection (window.search_local_map), so the localisation sees more of the map than the frame-to-frame match
+    handed over."""
     intr_opt = np.array(intr_init, dtype=np.float64)
     summaries = []
     pending = list(keyframes)
@@ -113,6 +116,8 @@ def run_pipeline(keyframes, landmarks, intr_init, gt_text: str, solve, frame_fre
             keyframes.append(pending.pop(0))
             if align is not None:
                 window.track_keyframe(len(keyframes) - 1, keyframes, landmarks, align, seen, match=match)
+            if search is not None:
+                window.search_local_map(len(keyframes) - 1, keyframes, landmarks, intr_opt, IMAGE_W, IMAGE_H, search)
             if localize is not None:
                 window.localize_keyframe(len(keyframes) - 1, keyframes, landmarks, intr_opt, localize, seen)
             if align is not None or localize is not None:

@@ -18,6 +18,7 @@ from .capi import (COV_INTR, LOG_FIELDS, RES_ERR_N, RES_OUTLIER, RES_STAT_N, BaC
                    BaPtsInfo, BaPtsRequest, PTS_STAT_N, BaPgInfo, BaPgProblem, BaPgRequest,
                    ALIGN_STAT_N, BaAlignInfo, BaAlignProblem, BaAlignRequest,
                    MATCH_COUNT_N, MATCH_KINDS, BaMatchInfo, BaMatchProblem, BaMatchRequest,
+                   GMATCH_COUNT_N, BaGmatchInfo, BaGmatchProblem, BaGmatchRequest,
                    BaOptions, BaPrepareInfo, BaResInfo, BaResRequest, BaSummary, ProblemArrays)
 
 
@@ -409,6 +410,99 @@ class Solver:
         out["matches"] = None if mlist is None else mlist[: info.n_matches]
         out["match_begin"] = mbegin
         out["pair_counts"] = None if pcounts is None else pcounts[:P]
+        return out
+
+    def guided_match(self, points, pt_desc, kp_uv, kp_desc, frame_pose, intr, width: int, height: int,
+                     frame_range=None, cand=None, kp_depth=None, kind: str = "hamming", radius: float = 15.0,
+                     ratio: float = 0.7, max_distance: int = 0, min_depth: float = 0.0, depth_tol: float = 0.0,
+                     one_to_one: bool = True, cell_px: int = 0, matches: bool = True, counts: bool = False,
+                     proj: bool = False) -> dict:
+        """ba_guided_match: the descriptor search in a pixel window around projected landmarks. ``points`` (N, 3)
+        world-frame landmarks with ``pt_desc`` (N, B) uint8; ``kp_uv`` (K, 2) keypoint pixels with ``kp_desc`` (K, B)
+        and optionally ``kp_depth`` (K,); ``frame_pose`` (F, 7) ``T_w_c`` per frame entry; ``intr`` fx, fy, cx, cy of
+        the ``width`` x ``height`` image. ``frame_range`` (F, 2): entry f searches the keypoints [begin, end)
+        (``None``: all keypoints for every entry; equal ranges are binned once). ``cand``: per entry an array of
+        landmark indices (``None``: every landmark for every entry). ``kind`` and the distances are ``match``'s. A
+        landmark is matched to the nearest descriptor among the keypoints within ``radius`` pixels of its projection
+        (and within ``depth_tol`` relative depth, when > 0 and ``kp_depth`` is given), subject to the ratio test
+        against the window's second neighbour, ``max_distance`` and, with ``one_to_one``, to being the best row of
+        its entry for that keypoint. The context's plan and LM state are not touched. Returns the fields of
+        ``ba_gmatch_info``, ``cand_begin`` (F + 1,), ``cand_pt`` (n_rows,), ``nn_kp`` / ``nn_dist`` (n_rows, 2) int32
+        (keypoint indices inside the entry's range, -1 = none), ``status`` (n_rows,) uint8 (``capi.GMATCH_STATUS``),
+        ``n_in_window`` (n_rows,), ``matches`` (n_matches, 2) int32 (landmark index, keypoint inside the range) with
+        ``match_begin`` (F + 1,) (``None`` unless ``matches``), ``frame_counts`` (F, 9; ``None`` unless ``counts``)
+        and ``proj`` (n_rows, 3: u, v, z; ``None`` unless ``proj``)."""
+        i32p, u8p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+        if kind not in MATCH_KINDS:
+            raise ValueError(f"kind must be one of {sorted(MATCH_KINDS)}")
+        X = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        uv = np.ascontiguousarray(kp_uv, dtype=np.float64).reshape(-1, 2)
+        pd = np.ascontiguousarray(pt_desc, dtype=np.uint8)
+        kd = np.ascontiguousarray(kp_desc, dtype=np.uint8)
+        if pd.ndim != 2 or kd.ndim != 2 or pd.shape[1] != kd.shape[1] or len(pd) != len(X) or len(kd) != len(uv):
+            raise ValueError("pt_desc and kp_desc must be (n, desc_bytes) arrays of one descriptor size, one row per "
+                             "landmark / keypoint")
+        poses = np.ascontiguousarray(frame_pose, dtype=np.float64).reshape(-1, 7)
+        F = len(poses)
+        rng = np.tile(np.array([[0, len(uv)]], dtype=np.int32), (F, 1)) if frame_range is None else \
+            np.ascontiguousarray(frame_range, dtype=np.int32).reshape(-1, 2)
+        if len(rng) != F:
+            raise ValueError("frame_range must have one (begin, end) per frame pose")
+        if cand is None:
+            cand = [np.arange(len(X), dtype=np.int32)] * F
+        if len(cand) != F:
+            raise ValueError("cand must have one index array per frame pose")
+        cand = [np.asarray(c, dtype=np.int32).reshape(-1) for c in cand]
+        cand_begin = np.zeros(F + 1, dtype=np.int32)
+        if F:
+            cand_begin[1:] = np.cumsum([len(c) for c in cand])
+        cand_pt = np.ascontiguousarray(np.concatenate(cand) if F else np.zeros(0), dtype=np.int32)
+        n_rows = int(cand_begin[-1])
+        dep = None
+        if kp_depth is not None:
+            dep = np.ascontiguousarray(kp_depth, dtype=np.float64).reshape(-1)
+            if len(dep) != len(uv):
+                raise ValueError("kp_depth must have one value per keypoint")
+        g = BaGmatchProblem()
+        g.kind, g.desc_bytes, g.width, g.height = MATCH_KINDS[kind], kd.shape[1], int(width), int(height)
+        g.n_kp, g.n_points, g.n_frames, g.n_rows = len(uv), len(X), F, n_rows
+        g.intr[:] = [float(v) for v in np.asarray(intr, dtype=np.float64).reshape(4)]
+        for name, arr, t in (("kp_uv", uv, f64p), ("kp_desc", kd, u8p), ("kp_depth", dep, f64p), ("points", X, f64p),
+                             ("pt_desc", pd, u8p), ("frame_pose", poses, f64p), ("frame_range", rng, i32p),
+                             ("cand_pt", cand_pt, i32p)):
+            if arr is not None and arr.size:
+                setattr(g, name, arr.ctypes.data_as(t))
+        if F:
+            g.cand_begin = cand_begin.ctypes.data_as(i32p)
+        req, info = BaGmatchRequest(), BaGmatchInfo()
+        req.one_to_one, req.radius, req.ratio, req.max_distance = int(bool(one_to_one)), float(radius), float(ratio), int(max_distance)
+        req.min_depth, req.depth_tol, req.cell_px = float(min_depth), float(depth_tol), int(cell_px)
+        rows = max(n_rows, 1)
+        nn_kp = np.zeros((rows, 2), dtype=np.int32)
+        nn_dist = np.zeros((rows, 2), dtype=np.int32)
+        status = np.zeros(rows, dtype=np.uint8)
+        n_win = np.zeros(rows, dtype=np.int32)
+        req.nn_kp, req.nn_dist = nn_kp.ctypes.data_as(i32p), nn_dist.ctypes.data_as(i32p)
+        req.status, req.n_in_window = status.ctypes.data_as(u8p), n_win.ctypes.data_as(i32p)
+        mlist = mbegin = fcounts = pr = None
+        if matches:
+            mlist = np.zeros((rows, 2), dtype=np.int32)
+            mbegin = np.zeros(F + 1, dtype=np.int32)
+            req.matches, req.match_begin = mlist.ctypes.data_as(i32p), mbegin.ctypes.data_as(i32p)
+        if counts:
+            fcounts = np.zeros((max(F, 1), GMATCH_COUNT_N), dtype=np.int32)
+            req.frame_counts = fcounts.ctypes.data_as(i32p)
+        if proj:
+            pr = np.zeros((rows, 3), dtype=np.float64)
+            req.proj = pr.ctypes.data_as(f64p)
+        self._check(self._L.ba_guided_match(self._h, C.byref(g), C.byref(req), C.byref(info)), "ba_guided_match")
+        out = info.as_dict()
+        out["cand_begin"], out["cand_pt"] = cand_begin, cand_pt
+        out["nn_kp"], out["nn_dist"], out["status"], out["n_in_window"] = nn_kp[:n_rows], nn_dist[:n_rows], status[:n_rows], n_win[:n_rows]
+        out["matches"] = None if mlist is None else mlist[: info.n_matches]
+        out["match_begin"] = mbegin
+        out["frame_counts"] = None if fcounts is None else fcounts[:F]
+        out["proj"] = None if pr is None else pr[:n_rows]
         return out
 
     @staticmethod

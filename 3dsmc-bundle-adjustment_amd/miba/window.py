@@ -225,6 +225,40 @@ def track_keyframe(k: int, keyframes: list, landmarks: dict, align, seen=None, m
     return out
 
 
+def search_local_map(k: int, keyframes: list, landmarks: dict, intr, width: int, height: int, guided_match,
+                     n_recent: int = 5, **kw):
+    """ORB-SLAM's SearchByProjection against the local map: the landmarks keyframes ``k - n_recent .. k - 1`` observe
+    and keyframe ``k`` does not are projected into k with its pose as it stands and searched for among the keypoints
+    of k that map to no landmark (that subset is the call's keypoint range; the indices are mapped back afterwards):
+    ``guided_match(points, pt_desc, kp_uv, kp_desc, frame_pose, intr, width, height, kp_depth=..., **kw)`` -- a
+    ``miba.solver.Solver().guided_match``. A landmark's descriptor is that of its first observation
+    (``matching.landmark_descriptors``). The accepted matches are added to ``global_points_map``. Returns the call's
+    output with ``added``, the (local id, landmark id) pairs, or ``None`` when there is nothing to search (no
+    descriptors, no such landmark, no free keypoint)."""
+    kf = keyframes[k]
+    first = max(0, k - n_recent)
+    if k <= 0 or kf.descriptors is None:
+        return None
+    mine = set(kf.global_points_map.values())
+    ids, desc = matching.landmark_descriptors(keyframes[:k])
+    recent = set()
+    for other in keyframes[first:k]:
+        recent.update(other.global_points_map.values())
+    sel = np.array([i for i, l in enumerate(ids.tolist()) if l in recent and l not in mine], dtype=np.int64)
+    free = np.array([i for i in range(len(kf.keypoints)) if i not in kf.global_points_map], dtype=np.int64)
+    if not len(sel) or not len(free):
+        return None
+    points = np.array([landmarks[int(l)] for l in ids[sel]], dtype=np.float64).reshape(-1, 3)
+    loc = np.asarray(kf.points3d_local, dtype=np.float64).reshape(-1, 3)
+    out = dict(guided_match(points, desc[sel], np.asarray(kf.keypoints, dtype=np.float64).reshape(-1, 2)[free],
+                            np.asarray(kf.descriptors, dtype=np.uint8)[free], np.asarray(kf.T_w_c, dtype=np.float64).reshape(1, 7),
+                            intr, width, height, kp_depth=loc[free, 2], **kw))
+    out["added"] = [(int(free[kp]), int(ids[sel[pt]])) for pt, kp in np.asarray(out["matches"]).tolist()]
+    for local_id, landmark_id in out["added"]:
+        kf.global_points_map[local_id] = landmark_id
+    return out
+
+
 def refine_frame(k: int, keyframes: list, landmarks: dict, intr):
     """The landmarks keyframe ``k`` brings new evidence about, as ``ProblemArrays`` for a structure-only refinement
     (``None`` when nothing qualifies): the landmarks ``k`` observes that an earlier keyframe (index < k) also observes,

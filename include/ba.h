@@ -65,7 +65,9 @@ extern "C" {
  *   2, additive  ba_align with ba_align_problem, ba_align_request / ba_align_info (both sized structs): batched RANSAC
  *                relative pose from 3D-3D correspondences; ba_options and everything else unchanged.
  *   2, additive  ba_match with ba_match_problem, ba_match_request / ba_match_info (both sized structs): batched
- *                2-nearest-neighbour descriptor matching with the ratio test; everything else unchanged. */
+ *                2-nearest-neighbour descriptor matching with the ratio test; everything else unchanged.
+ *   2, additive  ba_guided_match with ba_gmatch_problem, ba_gmatch_request / ba_gmatch_info (both sized structs):
+ *                descriptor search in a pixel window around projected landmarks; everything else unchanged. */
 #define BA_API_VERSION 2
 
 /* error codes */
@@ -884,6 +886,99 @@ typedef struct ba_match_info {
 #define BA_MATCH_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 #define BA_MATCH_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
 int32_t ba_match(ba_context* ctx, const ba_match_problem* prob, const ba_match_request* req, ba_match_info* info);
+
+/* ---- guided match: descriptor search in a pixel window around projected landmarks ----
+ * What finds a landmark of the map in a frame whose pose is roughly known (ORB-SLAM's SearchByProjection / Fuse):
+ * project the landmark with the pose as it stands, look only at the frame's keypoints within `radius` pixels of the
+ * projection, take the best descriptor there. kind, desc_bytes and the two distances are ba_match's (BA_MATCH_HAMMING,
+ * BA_MATCH_L2_U8, a multiple of 4 in [4, BA_MATCH_MAX_BYTES]). One camera model (intr, width x height) per call.
+ * Rows. Frame entry f has the pose frame_pose[7 f ..] (T_w_c, Sophus order), the keypoints kp[begin..end)
+ * (frame_range, two values per entry) and the candidates cand_pt[cand_begin[f] .. cand_begin[f+1]) (landmark indices
+ * into points / pt_desc; cand_begin is non-decreasing from 0, n_rows = cand_begin[n_frames]). Output row r belongs to
+ * candidate r. Ranges of different entries may overlap or be equal: many pose hypotheses of one image are one copy
+ * of its keypoints (entries with equal ranges also share one binned grid on the device).
+ * Projection. The LM loop's and ba_residuals' sequence of operations, bit for bit: R from the unit quaternion,
+ * p = R^T (X - t), u = (cx z + fx x) (1/z), v = (cy z + fy y) (1/z). proj holds (u, v, z), u = v = 0 for status 1.
+ * Window. Keypoint k of the entry's range is in the row's window when, evaluated in f64 in this order with no fused
+ * multiply-add,
+ *     du = kp_u - u;  dv = kp_v - v;  (du * du) + (dv * dv) <= radius * radius
+ * and, when the depth gate is on (depth_tol > 0 and kp_depth given) and kp_depth[k] > 1e-15,
+ *     |kp_depth[k] - z| <= depth_tol * z.
+ * A keypoint without an admissible depth passes the gate. n_in_window counts the window's keypoints.
+ * Neighbours. The first and the second neighbour are the two smallest keypoints of the window under the
+ * lexicographic order (distance, keypoint index): independent of the binning and of any traversal order. nn_kp holds
+ * their indices inside the entry's range (k - begin), nn_dist the distances; -1 in both where there is none.
+ * Status. A row gets the first of these that applies:
+ *   0 accepted
+ *   1 z <= min_depth (or z is not a number)             (min_depth <= 0: 1e-15)
+ *   2 the projection is outside [0, width) x [0, height)
+ *   3 the window is empty
+ *   4 a second neighbour exists and ba_match's ratio test fails (HAMMING (float)d0 < ratio * (float)d1 in f32; L2_U8
+ *     (double)s0 < ((double)ratio * (double)ratio) * (double)s1 in f64; ratio <= 0: 0.7). A lone keypoint in the
+ *     window passes: here, unlike in ba_match, that is the good case.
+ *   5 max_distance > 0 and d0 > max_distance
+ *   6 with one_to_one: another row of the same frame entry passed 1-5, chose the same keypoint and has the smaller
+ *     key (d0, row)
+ * matches lists the accepted rows of each entry in candidate order as (cand_pt value, keypoint index inside the
+ * range); entry f's are matches[2 match_begin[f] .. 2 match_begin[f+1]). frame_counts, BA_GMATCH_COUNT_N per entry:
+ *   [0] n_cand   [1] n_kp   [2 + s] rows of status s, s = 0..6                    ([2] + .. + [8] = [0])
+ * cell_px is the side of the binning grid's cells (<= 0: the smallest power of two >= radius, at least 8, so that a
+ * window touches at most 3 x 3 cells). It is a speed knob only.
+ * Reproducibility. Floating point is used for the projection and the two gates alone, everything else is integer
+ * work with integer atomics: two calls give the same bits, an entry's rows do not depend on the other entries of the
+ * call nor on cell_px. Stand-alone like ba_match: device buffers of its own, a ba_solve_prepared after it is bitwise
+ * the solve without it.
+ * ba_gmatch_info: n_frames, n_rows, n_matches (status 0 over all entries), kind, n_grids (distinct keypoint ranges
+ * binned), cell_px (as used), the timings as in ba_match_info (optional in the same way).
+ * Errors, BA_E_INVALID, in this order: a null argument, struct sizes below the minimum, contexts with landmark
+ * shards; negative sizes; kind; desc_bytes; width or height below 1; a radius that is not finite and positive; a
+ * null frame_pose / frame_range / cand_begin with entries; a frame_range that is reversed or leaves [0, n_kp); a
+ * cand_begin that does not start at 0, decreases, or does not end at n_rows; a null cand_pt with rows, a cand_pt
+ * outside [0, n_points); a null required buffer (kp_uv / kp_desc with keypoints, points / pt_desc with rows, nn_kp /
+ * nn_dist / status with rows, match_begin with matches); more than 2^31 - 1 grid cells, binned keypoints or
+ * one-to-one slots over the call, or 2^24 or more entries (one workgroup of 256 threads each: the launch limit of
+ * 2^32 threads). Empty ranges, empty candidate lists and n_frames = 0 return 0. */
+#define BA_GMATCH_COUNT_N 9
+typedef struct ba_gmatch_problem {
+    int32_t kind, desc_bytes;          /* as ba_match_problem's                                           */
+    int32_t width, height;             /* pixels                                                          */
+    int32_t n_kp, n_points;            /* keypoints / landmarks                                           */
+    int32_t n_frames, n_rows;          /* n_rows = cand_begin[n_frames]                                   */
+    double intr[4];                    /* fx, fy, cx, cy                                                  */
+    const double* kp_uv;               /* [n_kp*2]                                                        */
+    const uint8_t* kp_desc;            /* [n_kp*desc_bytes]                                               */
+    const double* kp_depth;            /* optional [n_kp]                                                 */
+    const double* points;              /* [n_points*3] world frame                                        */
+    const uint8_t* pt_desc;            /* [n_points*desc_bytes]                                           */
+    const double* frame_pose;          /* [n_frames*7] T_w_c: qx qy qz qw tx ty tz                        */
+    const int32_t* frame_range;        /* [n_frames*2] keypoint begin, end                                */
+    const int32_t* cand_begin;         /* [n_frames+1]                                                    */
+    const int32_t* cand_pt;            /* [n_rows] landmark indices                                       */
+} ba_gmatch_problem;
+typedef struct ba_gmatch_request {
+    int32_t struct_size, one_to_one;   /* BA_GMATCH_REQUEST_INIT; one_to_one 0 / 1                        */
+    double radius;                     /* pixels, > 0                                                     */
+    float ratio; int32_t max_distance; /* ratio <= 0: 0.7f; max_distance <= 0: no limit                   */
+    double min_depth, depth_tol;       /* min_depth <= 0: 1e-15; depth_tol <= 0: no depth gate            */
+    int32_t cell_px, reserved0;        /* cell_px <= 0: the default                                       */
+    int32_t* nn_kp;                    /* [n_rows*2] out: keypoint index inside the range, -1 = none      */
+    int32_t* nn_dist;                  /* [n_rows*2] out: the distances, -1 = none                        */
+    uint8_t* status;                   /* [n_rows] out                                                    */
+    double* proj;                      /* optional [n_rows*3] out: u, v, z                                */
+    int32_t* n_in_window;              /* optional [n_rows] out                                           */
+    int32_t* matches;                  /* optional [n_rows*2] out: accepted (cand_pt value, keypoint in range) */
+    int32_t* match_begin;              /* optional [n_frames+1] out (required with matches)               */
+    int32_t* frame_counts;             /* optional [n_frames*BA_GMATCH_COUNT_N] out                       */
+} ba_gmatch_request;
+typedef struct ba_gmatch_info {
+    int32_t struct_size, n_frames, n_rows, n_matches, kind, n_grids, cell_px, reserved0;
+    double time_kernels_ms, time_total_ms;
+} ba_gmatch_info;
+#define BA_GMATCH_REQUEST_MIN_SIZE ((int32_t)sizeof(ba_gmatch_request))
+#define BA_GMATCH_INFO_MIN_SIZE ((int32_t)offsetof(ba_gmatch_info, time_kernels_ms))
+#define BA_GMATCH_REQUEST_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+#define BA_GMATCH_INFO_INIT(s) (memset(&(s), 0, sizeof(s)), (s).struct_size = (int32_t)sizeof(s))
+int32_t ba_guided_match(ba_context* ctx, const ba_gmatch_problem* prob, const ba_gmatch_request* req, ba_gmatch_info* info);
 
 /* ---- verification hooks (used by the parity tests; not on the hot path) ----
  * Evaluate per-observation robustified residuals and local Jacobians on the
